@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE ONLY -- import shim for the *real* reference at /root/reference.
 
 Used only in the build container (where /root/reference exists) by
-``oracle/make_golden.py`` and by ``tests/test_oracle_vs_reference.py`` to pin the oracle
+``oracle/make_golden.py`` and ``oracle/make_golden_oracle_check.py`` to pin the oracle
 restatement (``oracle/dav2_oracle.py``) against the reference itself.  Nothing here is
 importable on the GPU box (the reference does not travel) and nothing in the product
 package may import this module.

@@ -7,9 +7,9 @@ it.  The product package never does (it has no CPU fallback at all).
 
 Parity pinning: the reference ships no tests or golden vectors for this path,
 so the oracle is pinned against the reference *itself*, imported in the build container via
-``oracle/_refshim.py``: ``tests/test_oracle_vs_reference.py`` compares them tensor-for-tensor
-when /root/reference is present, and ``oracle/make_golden.py`` commits the reference's outputs
-as fixtures under ``tests/golden/`` which ``tests/test_oracle_golden.py`` re-checks anywhere.
+``oracle/_refshim.py``: ``oracle/make_golden.py`` and ``oracle/make_golden_oracle_check.py`` commit
+the reference's outputs as fixtures under ``tests/golden/``, which ``tests/test_oracle_golden.py`` and
+``tests/test_oracle_vs_reference.py`` re-check anywhere.
 
 All citations are relative to /root/reference/; DA2 = src/models/amodalsynthdrive/depth_anything_v2,
 RAW = src/models/amodalsynthdrive/depth_anything_v2_raw.

@@ -6,6 +6,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import torch
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -37,3 +40,31 @@ def test_bench_launcher_reports_a_failing_rank():
     r = _run({}, "--gpus", "2", "--steps", "1", "--warmup", "0", "--batch", "2", "--size", "-1", "--repeats", "0")
     assert r.returncode != 0
     assert not any(ln.startswith("{") and '"metric"' in ln for ln in r.stdout.splitlines())
+
+
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    # a plain run times exactly --steps steps, reports ms_per_step and nothing beyond the headline; --dump-outputs writes the maps of its last step
+    lines, dumps = [], []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = _run({}, "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2", "--size", "28", "--dump-outputs", str(d))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+        dumps.append(np.load(d / "depth.npy"))
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and abs(line["value"] - 2 * 1e3 / line["ms_per_step"]) < 1e-6 * line["value"]
+    assert line["ms_per_step_repeats"] == [] and line["rel_l1"] is None and "roofline" not in line and "cpu_baseline" not in line
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (2, 1, 28, 28) and np.array_equal(dumps[0], dumps[1])
+
+
+def test_bench_dump_samples_whole_images_past_the_cap(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    out = torch.arange(10 * 4 * 4, dtype=torch.float32).view(10, 1, 4, 4)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 3 * 4 * 4 * 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out)
+    idx = np.load(tmp_path / "a" / "depth_index.npy").astype(np.int64)
+    got = np.load(tmp_path / "a" / "depth.npy")
+    assert got.dtype == np.float32 and got.shape == (3, 1, 4, 4) and np.array_equal(got, out.numpy()[idx])
+    assert np.array_equal(got, np.load(tmp_path / "b" / "depth.npy"))
