@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 
 # --- constants mirrored from include/ada_hip.h ------------------------------------------------
-ABI_VERSION = 8
+ABI_VERSION = 9
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 A_PLAIN, A_CONV3 = 0, 1
 MAP_PLAIN, MAP_PAD, MAP_TOKEN, MAP_SHUFFLE = 0, 1, 2, 3
@@ -29,6 +29,7 @@ EXPORTS = (
     "ada_abi_version", "ada_operand_dtype", "ada_last_error", "ada_igemm", "ada_attention_fwd", "ada_attention_ex",
     "ada_pos_embed_resize", "ada_layernorm_fwd", "ada_layernorm_ex", "ada_patchify", "ada_write_cls", "ada_bilinear_fwd", "ada_selftest",
     "ada_minmax_fwd", "ada_depth_stats_fwd", "ada_token_diversity_fwd", "ada_normalize_fwd", "ada_blend_fwd", "ada_depth_eval_fwd", "ada_tile_blend_fwd", "ada_dpt_tail_fwd", "ada_tapsum_resize_fwd",
+    "ada_image_prep_fwd", "ada_depth_resize_fwd",
     "ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_last_tile",
     "ada_debug_set_timestamps", "ada_debug_set_attention_variant", "ada_debug_count_saturated",
 )
@@ -143,6 +144,11 @@ def load(path: Optional[str] = None):
     lib.ada_tapsum_resize_fwd.restype = c_int
     lib.ada_depth_eval_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_float, c_float, c_void_p, c_void_p]
     lib.ada_depth_eval_fwd.restype = c_int
+    lib.ada_image_prep_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32, c_int32,
+                                       ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p, c_void_p]
+    lib.ada_image_prep_fwd.restype = c_int
+    lib.ada_depth_resize_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]
+    lib.ada_depth_resize_fwd.restype = c_int
     for name in ("ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_set_attention_variant"):
         getattr(lib, name).argtypes = [c_int]
         getattr(lib, name).restype = None
@@ -404,6 +410,24 @@ def depth_eval(pred, gt, mask=None, scale_shift=None, clip=None) -> torch.Tensor
                                      _dev(scale_shift, "scale_shift", torch.float32) if scale_shift is not None else None,
                                      lo, hi, _dev(sums, "sums", torch.float64), _stream()), "ada_depth_eval_fwd")
     return sums
+
+
+def image_prep(src, batch, hi, wi, channels, row_pitch, image_stride, ho, wo, mean, std, out):
+    """uint8 BGR(A) HWC images (rows ``row_pitch`` bytes apart, images ``image_stride`` bytes apart; ``src`` points at pixel (0, 0) of image 0) ->
+    out fp32 [batch, 3, ho, wo]: RGB / 255, cv2 INTER_CUBIC resize, (v - mean) / std (ada_image_prep_fwd)."""
+    m = (c_float * 3)(*mean)
+    sd = (c_float * 3)(*std)
+    _check(load().ada_image_prep_fwd(_dev(src, "src", torch.uint8), batch, hi, wi, channels, row_pitch, image_stride, ho, wo, m, sd,
+                                     _dev(out, "out", torch.float32), _stream()), "ada_image_prep_fwd")
+
+
+def depth_resize(inp, out):
+    """inp fp32 [B, hi, wi] -> out fp32 [B, ho, wo], both contiguous: bilinear, align_corners=True, ATen's arithmetic (ada_depth_resize_fwd)."""
+    if not (inp.is_contiguous() and out.is_contiguous()) or inp.dim() != 3 or out.dim() != 3 or inp.shape[0] != out.shape[0]:
+        raise HipExtError(f"depth_resize: contiguous [B, H, W] tensors required, got {tuple(inp.shape)} -> {tuple(out.shape)}")
+    B, hi, wi = inp.shape
+    _check(load().ada_depth_resize_fwd(_dev(inp, "in", torch.float32), B, hi, wi, out.shape[1], out.shape[2], _dev(out, "out", torch.float32), _stream()),
+           "ada_depth_resize_fwd")
 
 
 # --- tuning / diagnostic hooks (include/ada_hip.h, last section) ---------------------------------

@@ -3,6 +3,7 @@
 caller (reference infer.py:19); head ends in ReLU and forward applies F.relu + squeeze(1) again
 (RAW/dpt.py:182-184).  Shares every layer class with the guided package: the reference keeps a verbatim
 second copy of the tree, which differs only in the guidance embed, input_projection and the tail."""
+import torch
 import torch.nn as nn
 
 from ..depth_anything_v2.dinov2 import DINOv2 as _DINOv2
@@ -37,3 +38,21 @@ class DepthAnythingV2(_EngineMixin, nn.Module):
         ph, pw = x.shape[-2] // 14, x.shape[-1] // 14
         feats = self.pretrained.get_intermediate_layers(x, self.intermediate_layer_idx[self.encoder], return_class_token=True)
         return self.depth_head(feats, ph, pw).squeeze(1)
+
+    @torch.no_grad()
+    def infer_image(self, raw_image, input_size=518):
+        """Reference RAW/dpt.py:186-194: depth of one decoded photo at the photo's own resolution, float32 numpy [h, w].  ``raw_image``: uint8
+        BGR [h, w, 3] or BGRA [h, w, 4] (alpha dropped), a numpy array or a torch tensor on the model's device (see image2tensor).  The depth map
+        is resized back on the device (ada_depth_resize_fwd); the only host synchronisation is the final copy, as in the reference."""
+        from hip_ext.image import resize_depth
+        image, (h, w) = self.image2tensor(raw_image, input_size)
+        depth = self.forward(image, normalise_input=False)     # image2tensor normalised it already, whatever self.normalise_input says
+        return resize_depth(depth, h, w)[0].cpu().numpy()
+
+    def image2tensor(self, raw_image, input_size=518):
+        """Reference RAW/dpt.py:196-221: (ImageNet-normalised fp32 [1, 3, H, W] on the model's device, (h, w)), H x W the multiple-of-14 size
+        the reference's Resize(keep_aspect_ratio, lower_bound) picks (hip_ext.image.network_size).  BGR -> RGB, / 255, cv2's INTER_CUBIC resize
+        and the normalisation run in one kernel (ada_image_prep_fwd).  Only uint8 images are accepted (TypeError / ValueError otherwise; the
+        reference would divide any dtype by 255); a numpy array is copied to the device, a device tensor is read in place at its row stride."""
+        from hip_ext.image import image_to_tensor
+        return image_to_tensor(raw_image, input_size, next(self.parameters()).device)

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ADA_ABI_VERSION 8   /* 8 (round 6): the default-off experiment paths that lost are gone -- ada_igemm_args without ln_stats / ln_colsum / rowstat_out (EP_LNFOLD / EP_ROWSTATS) and the LayerNorm tail (ln_*), no ada_rowstats_finalize.  History: 6 (round 5): + ada_depth_stats_fwd, ada_token_diversity_fwd; 7: ada_igemm_args grows f8_from / f8_mid / f8_scales at its end and split_seg < 0 names the fp8 form of a split output (a zero-filled tail = off: every ABI-6 call means what it meant) */
+#define ADA_ABI_VERSION 9   /* 9: + ada_image_prep_fwd, ada_depth_resize_fwd (the raw model's infer_image; exports only, no signature changed).  History: 8 (round 6): the default-off experiment paths that lost are gone -- ada_igemm_args without ln_stats / ln_colsum / rowstat_out (EP_LNFOLD / EP_ROWSTATS) and the LayerNorm tail (ln_*), no ada_rowstats_finalize.  History: 6 (round 5): + ada_depth_stats_fwd, ada_token_diversity_fwd; 7: ada_igemm_args grows f8_from / f8_mid / f8_scales at its end and split_seg < 0 names the fp8 form of a split output (a zero-filled tail = off: every ABI-6 call means what it meant) */
 
 /* status codes */
 #define ADA_OK 0
@@ -365,6 +365,27 @@ int ada_depth_stats_fwd(const float* in, int32_t batch, int64_t n_per_image, int
  * chunks; sum Var / sum E[t^2] ~ 0.02 marks inputs whose patch tokens are all alike (constant images), where the head's operand rounding errors add
  * coherently: the second trigger of hip_ext/engine.py's precision ladder.  No reference counterpart. */
 int ada_token_diversity_fwd(const void* tap, int64_t ld, int32_t batch, int32_t rows_per_image, int32_t dim, float* sums, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Image preparation and depth read-out of the raw model's infer_image / image2tensor (RAW/dpt.py:186-221), which the reference does on
+ * the host with OpenCV and numpy (RAW/util/transform.py:5-158):
+ *   ada_image_prep_fwd    cv2.cvtColor(BGR2RGB) / 255.0, cv2.resize(INTER_CUBIC) to ho x wo, (v - mean) / std, HWC -> CHW    (RAW/dpt.py:210-214)
+ *     src      uint8 HWC [B][hi][wi][channels], BGR (channels = 3) or BGRA (4: alpha ignored, as cvtColor(BGR2RGB) does); pixels packed, rows
+ *              row_pitch_bytes apart (>= wi * channels: a crop of a decoded frame is read in place), images image_stride_bytes apart
+ *     out      fp32 NCHW [B, 3, ho, wo], RGB order.  mean / std: [3] fp32 HOST pointers, RGB order
+ *     OpenCV's float path of INTER_CUBIC: scale_x = 1 / ((double)wo / wi); fx = (float)((dx + 0.5) * scale_x - 0.5), sx = floor(fx), fx -= sx;
+ *     taps sx - 1 .. sx + 2 clamped to the image (fx is kept at the borders); fp32 coefficients of cv2's interpolateCubic (A = -0.75);
+ *     horizontal pass, then vertical (the same for y).  No antialiasing, and the result is NOT clamped: the overshoot of the cubic kernel
+ *     at edges (below 0, above 1 before normalisation) is kept, as the reference keeps it.  Accumulation is fp32 (cv2: float64).
+ *   ada_depth_resize_fwd  F.interpolate(depth[:, None], (ho, wo), mode="bilinear", align_corners=True)                        (RAW/dpt.py:192)
+ *     in fp32 [B, hi, wi] -> out fp32 [B, ho, wo], both contiguous; ATen's arithmetic: scale = (in - 1) / (out - 1) in fp32 (0 when out == 1),
+ *     src = scale * dst, i0 = (int)src, i1 = i0 + (i0 < in - 1), lambda = src - i0.  Any size in either direction (one channel: ada_bilinear_fwd
+ *     needs channels % 4 == 0 and at most 2^24 output pixels).
+ * Both: ho <= 262140, batch <= 65535.
+ * ---------------------------------------------------------------------------------------- */
+int ada_image_prep_fwd(const uint8_t* src, int32_t batch, int32_t hi, int32_t wi, int32_t channels, int64_t row_pitch_bytes,
+                       int64_t image_stride_bytes, int32_t ho, int32_t wo, const float* mean, const float* std, float* out, void* stream);
+int ada_depth_resize_fwd(const float* in, int32_t batch, int32_t hi, int32_t wi, int32_t ho, int32_t wo, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Tiled inference for inputs larger than the network's native 518 x 518 (the reference squashes every
