@@ -41,6 +41,7 @@ from . import patchify as k_patchify
 from . import pos_embed_resize as k_pos_embed_resize
 from . import tapsum_resize as k_tapsum_resize
 from . import write_cls as k_write_cls
+from .ladder import ladder_curve, ladder_decide, ladder_thresholds, next_start_rung, rung_counts  # noqa: F401  (ladder_curve: re-exported)
 
 _probe = None   # list of (label, device counter) while DepthEngine.saturation_report runs, else None
 
@@ -163,7 +164,7 @@ class PackedWeights:
                  enc_split_blocks: int = 0, head_only: bool = False, tap_split: bool = False,
                  f8: str = "both", tap_f8: Optional[bool] = None, f8_only=None):
         op = operand_dtype()
-        # head_only: the DPT head's weights only (the second rung of the precision ladder, DepthEngine._escalate, re-runs the head from the taps)
+        # head_only: the DPT head's weights only (the second rung of the precision ladder, DepthEngine._ladder, re-runs the head from the taps)
         # tap_split: the four taps are stored [hi | lo] whatever the head's own policy -- so that a split-precision head can be re-run from them
         self.head_only, self.tap_split = bool(head_only), bool(tap_split)
         cfg = VIT[encoder]
@@ -579,7 +580,7 @@ class Workspace:
 # fill 0.04-0.7 of a round of the 256 CUs (profiles/r05_e_config2_shapes.txt), so below HEAD_STREAMS_ROWS patch rows they are issued on four HIP streams
 # (fork / join with events: capturable into the forward's graph) and the coarse levels run in the CUs the fine level leaves idle.  Same kernels, same
 # arguments, same bits.  ADA_HEAD_STREAMS=0 / 1: never / always.
-# _second_rung_first: relative guard band around the ladder's thresholds inside which the first rung's own r decides (the rungs' maps differ by ~1e-3 of their logits)
+# hip_ext.ladder.ladder_decide: relative guard band around the ladder's thresholds inside which a higher rung's r does not decide and the first rung's own r does (the rungs' maps differ by ~1e-3 of their logits)
 LADDER_GUARD = float(os.environ.get("ADA_LADDER_GUARD", "0.02"))
 # ADA_LADDER_STICKY=0: always run the first rung's head first (A/B)
 LADDER_STICKY = os.environ.get("ADA_LADDER_STICKY", "1") != "0"
@@ -637,61 +638,6 @@ class _GraphedForward:
             return out if post is None else post(self.ws, out, x, guide)
 
 
-def ladder_curve(zk: torch.Tensor, z3: torch.Tensor, act: int):
-    """The calibration's raw material (DepthEngine.calibrate; pure torch, any device): for every image [n, ...] and every shift d of the grid, (r, e) =
-    (the image's sensitivity  sum w(z3 + d) / sum |f(z3 + d)|,  the metric  sum |f(zk + d) - f(z3 + d)| / sum |f(z3 + d)|  of rung k against the third),
-    f / w = sigmoid / s(1-s), ReLU / [z > 0], identity / 1.  Returns R, E as [n, shifts] float64 tensors."""
-    a, t = zk.flatten(1).double(), z3.flatten(1).double()
-    if act == ACT_NONE:      # a shift of bare logits changes nothing but the denominator: one point per image, e = eps r exactly
-        den = t.abs().sum(1).clamp_min(1e-300)
-        return (t.shape[1] / den).unsqueeze(1), ((a - t).abs().sum(1) / den).unsqueeze(1)
-    if act == ACT_SIGMOID:      # shifts that put the map's mean between ~0.9 and ~0.02 -- in units of the logits' own spread where that is wide, so that r reaches -> 1
-        scale = t.std(dim=1, keepdim=True).clamp_min(1.0)
-        grid = -t.median(dim=1, keepdim=True).values + scale * torch.linspace(-5.0, 2.0, 29, dtype=t.dtype, device=t.device)[None, :]
-    else:                       # ReLU: shifts that leave 97 % ... 3 % of the map positive
-        qs = torch.tensor([0.03, 0.08, 0.15, 0.25, 0.35, 0.5, 0.65, 0.75, 0.85, 0.92, 0.97], dtype=t.dtype, device=t.device)
-        grid = -torch.quantile(t, qs, dim=1).t()
-    R, Em = [], []
-    for j in range(grid.shape[1]):
-        d = grid[:, j:j + 1]
-        if act == ACT_SIGMOID:
-            fa, ft = torch.sigmoid(a + d), torch.sigmoid(t + d)
-            wsum = (ft * (1 - ft)).sum(1)
-        else:
-            fa, ft = (a + d).clamp_min(0), (t + d).clamp_min(0)
-            wsum = (ft > 0).double().sum(1)
-        den = ft.sum(1).clamp_min(1e-300)
-        R.append(wsum / den)
-        Em.append((fa - ft).abs().sum(1) / den)
-    return torch.stack(R, 1), torch.stack(Em, 1)
-
-
-def ladder_thresholds(z1: torch.Tensor, z2: Optional[torch.Tensor], z3: torch.Tensor, act: int, budget: float, safety: float, rule: str = "cross") -> dict:
-    """Thresholds of the precision ladder from the logits of the rungs on the calibration images (see DepthEngine.calibrate): per rung k the largest eps = e / r over
-    the points, the `global` threshold budget / (safety eps_max) and the `cross` threshold -- the smallest r at which a calibration point has safety * e > budget (the
-    rung's error AT the operating point where it would be left, not its worst anywhere; inf when no point exceeds the budget).  r from rung 1, r3 from rung 2 (no
-    second rung: r3 from rung 1).  A sigmoid's r lives in (0, 1): its thresholds are capped at 0.97.  Pure torch: unit-tested on the CPU."""
-    if rule not in ("cross", "global"):
-        raise HipExtError(f"ladder_thresholds: rule={rule!r} (cross | global)")
-
-    def one(zk):
-        R, Em = ladder_curve(zk, z3, act)
-        eps_max = float((Em / R.clamp_min(1e-300)).max())
-        bad = Em * safety > budget
-        return eps_max, budget / (safety * max(eps_max, 1e-30)), (float(R[bad].min()) if bool(bad.any()) else float("inf"))
-    cap = (lambda v, lo: min(max(v, lo), 0.97)) if act == ACT_SIGMOID else (lambda v, lo: max(v, lo))
-    pick = (lambda g, c: c if rule == "cross" else g)
-    e1, g1, c1 = one(z1)
-    res = dict(budget=budget, safety=safety, rule=rule, eps1=e1, r_global=g1, r_cross=c1, act={ACT_SIGMOID: "sigmoid", ACT_RELU: "relu", ACT_NONE: "none"}[act])
-    if z2 is not None:
-        e2, g2, c2 = one(z2)
-        r = cap(pick(g1, c1), 0.02)
-        res.update(eps2=e2, r3_global=g2, r3_cross=c2, r=r, r3=cap(pick(g2, c2), r))
-    else:
-        res.update(r3=cap(pick(g1, c1), 0.0))
-    return res
-
-
 class DepthEngine:
     """Runs one forward.  ``final_act``: 'sigmoid' | 'relu' | 'none'."""
 
@@ -699,14 +645,14 @@ class DepthEngine:
         self.w = weights
         self.final_act = {"sigmoid": ACT_SIGMOID, "relu": ACT_RELU, "none": ACT_NONE}[final_act]
         self.normalise_input = normalise_input
-        # Precision ladder of the sigmoid heads (see _escalate): dict(r=<threshold on sum s(1-s) / sum s>, make=<callable -> head-only PackedWeights
+        # Precision ladder of the sigmoid heads (see _ladder): dict(r=<threshold on sum s(1-s) / sum s>, make=<callable -> head-only PackedWeights
         # in split precision>) or None.  The first rung -- this engine's own weights -- must keep its taps [hi | lo] (PackedWeights.tap_split).
         # Heads without a sigmoid keep the third rung's token-diversity trigger only: dict(div=..., make3=...) (DA2/dpt.py::_flat_input_rung).
         self.ladder = ladder
         self._warned = False          # the one-time notice that images are being re-run
         self.second_rung_first_calls = 0     # calls that ran the second rung's head first (diagnostic)
         self.third_rung_first_calls = 0      # ... the third-rung engine first
-        self._start_rung = 1          # which head runs first (_run_ladder): 2 after a call most of whose images left the first rung
+        self._start_rung = 1          # which rung runs first (_ladder; hip_ext.ladder.next_start_rung): 2 after a call most of whose images left the first rung
         if self.ladder is not None and "make" in self.ladder and not weights.tap_split and "proj" not in weights.split:
             raise HipExtError("precision ladder: the engine's weights must be packed with tap_split=True")
         self._w_hi: Optional[PackedWeights] = None
@@ -717,7 +663,7 @@ class DepthEngine:
         self.escalated3 = 0           # ... of which on the third rung
         self.tap_f8 = bool(weights.tap_f8)   # the taps (and with them the second rung's products) carry fp8 correction terms
         self.last_ratio = None        # per-image sum s(1-s) / sum s of the most recent call (CPU tensor), None when the ladder is off
-        self.last_diversity = None    # per-image token diversity of the last tap (see _escalate)
+        self.last_diversity = None    # per-image token diversity of the last tap (see _image_stats)
         self.last_input_diversity = None   # ... and of the patchified input
         self._ws: "OrderedDict[tuple, Workspace]" = OrderedDict()
         self._graphs: "OrderedDict[tuple, object]" = OrderedDict()   # key -> _GraphedForward | False (capture refused) | int (sightings)
@@ -818,7 +764,7 @@ class DepthEngine:
         use = mode == "1" or (mode == "auto" and self.w.encoder in GRAPH_AUTO_ENCODERS and x.shape[0] * x.shape[-2] * x.shape[-1] <= GRAPH_AUTO_PIXELS)
         # replay bypasses the Python wrappers: with a KernelTimer or a tile log attached the launches must be issued one by one
         if not use or instrumented() or torch.cuda.is_current_stream_capturing():
-            return self._run_ladder(x, guide, norm)
+            return self._ladder(x, guide, norm)
         # the kernel variant / tile override / fused-tail switch in force at capture time are baked into the graph
         key = (tuple(x.shape), None if guide is None else tuple(guide.shape), str(x.device), debug_epoch(), FUSED_TAIL, SUBPIXEL, OC1_COMMUTE, norm)
         with self._lock:
@@ -841,101 +787,179 @@ class DepthEngine:
                 while len(self._graphs) > max(1, MAX_GRAPHS):
                     self._graphs.popitem(last=False)
         if g is False:
-            return self._run_ladder(x, guide, norm)
-        return g(x, guide, (lambda ws_, out_, x_, g_: self._escalate(ws_, out_, x_, g_, norm)) if self.ladder is not None else None)
+            return self._ladder(x, guide, norm)
+        return g(x, guide, (lambda ws_, out_, x_, g_: self._ladder(x_, g_, norm, first=(ws_, out_))) if self.ladder is not None else None)
 
-    def _escalate(self, ws: Optional[Workspace], out: torch.Tensor, x: Optional[torch.Tensor] = None, guide: Optional[torch.Tensor] = None,
-                  norm: Optional[bool] = None) -> torch.Tensor:
-        """Second rung of the precision ladder (sigmoid heads).  The default policy runs the DPT head on single fp16 operands and
-        counts on the sigmoid to compress the logit error it leaves (~1.2e-3 mean absolute): in the north-star metric mean|a - b| / mean|b| that error
-        arrives multiplied by  r = sum s (1 - s) / sum s  of the image -- 0.3-0.5 for maps that span (0, 1), -> 1 for maps concentrated near 0, where the
-        single-precision head exceeds the 1e-3 bar (reference fixtures vitl_518_m10, vitb_518_zeros, ...).  r is computed from the output itself
-        (ada_depth_stats_fwd, one deterministic reduction); for the images whose r exceeds the threshold the HEAD ONLY (27 % of the FLOPs) is re-run
-        in split precision from the four taps, which this engine keeps [hi | lo] for the purpose, and its result replaces theirs.  The decision is a
-        pure function of the image's own first-rung results: deterministic, independent of the rest of the batch.  Second trigger: the TOKEN DIVERSITY
-        of the last tap (ada_token_diversity_fwd: sum of the feature columns' variances over the image's patch tokens / sum of their mean squares) --
-        0.23-0.53 on noise and image-like inputs, 0.02 on constant and checkerboard images, where every patch token is the same up to its position
-        and the head's rounding errors add coherently over positions (ViT-B, all-zero input at output mean 0.50: 1.29e-3 on the first rung, 3.6e-4 on
-        the second; profiles/r05_h_*) -- such an image now goes to the THIRD rung, below.  Costs one host read of ~50 floats per image (the forward's only synchronisation); off under stream capture
-        (a caller's own HIP graph cannot hold a data-dependent branch).
-        THIRD RUNG (round 5, held-out draws of the output-range sweep): at the very bottom of the range -- maps averaging 0.03-0.06, r > 0.75 -- nothing is
-        left of the sigmoid's compression and the second rung's own logit error (0.8e-3 ... 1.2e-3, the ENCODER's fp16 operand rounding: ViT-B on a constant
-        image at mean 0.03: 1.1e-3 with the whole head in split precision) is what shows.  Images with r above lad["r3"] are therefore run again as a
-        whole, encoder blocks and head in split precision (lad["make3"]: an engine of its own, built on first use; 1.6e-4 ... 3.7e-4 on the cases that
-        exposed it, profiles/r05_v_third_rung_probe.txt), instead of taking the second rung."""
+    # ---- precision ladder: the rungs run here, every decision is hip_ext.ladder's ----------------------
+    def _second_weights(self) -> PackedWeights:
+        """The second rung's head-only weights, packed on first use."""
+        if self._w_hi is None:
+            self._w_hi = self.ladder["make"]()
+        return self._w_hi
+
+    def _third_engine(self) -> "DepthEngine":
+        """The third rung: an engine of its own with every encoder block and the whole head in split precision, built on first use."""
+        if self._eng3 is None:
+            self._eng3 = self.ladder["make3"]()
+        return self._eng3
+
+    @staticmethod
+    def _third_workspace(eng3: "DepthEngine", out: torch.Tensor) -> Workspace:
+        """The workspace behind the output ``eng3.forward`` has just returned -- looked up by shape (a replayed graph of eng3 writes the one it captured, which an
+        LRU eviction can have replaced under this key: ADVICE.md)."""
+        return eng3.workspace(out.shape[0], out.shape[-2], out.shape[-1], out.device)
+
+    def _image_stats(self, eng: "DepthEngine", ws: Workspace, out: torch.Tensor):
+        """The ladder's per-image statistics of one rung's run -- ``out`` and the full workspace ``ws`` of ``eng`` (this engine or the third rung's) that produced it:
+        one deterministic reduction each, ONE host read of (8 + D / 64 + patch width / 64) x 2 floats per image (the forward's only synchronisation).  Returns
+        (r, flat, tap_div, in_div), float64 / bool CPU tensors per image:
+        r -- the sensitivity of the metric mean|a - b| / mean|b| to a logit error, from the output itself (ada_depth_stats_fwd): sum s(1-s) / sum s behind a sigmoid
+        (0.3-0.5 for maps that span (0, 1), -> 1 for maps near 0, where nothing is left of the sigmoid's compression), (positive outputs) / sum out behind a ReLU (a
+        clipped pixel carries no error; a map that is mostly clipped with the rest just above the kink has a small denominator), N / sum |out| for bare logits; zeros
+        while the ladder has no r threshold.
+        tap_div -- the TOKEN DIVERSITY of the last tap (ada_token_diversity_fwd: sum of the feature columns' variances over the image's patch tokens / sum of their
+        mean squares): 0.23-0.53 on noise and image-like inputs, 0.02 on constant and checkerboard images, where every patch token is the same up to its position and
+        the rounding errors add coherently over positions; None without lad["div"].
+        in_div -- the same over the PATCHIFIED INPUT: the raw models' last tap does not tell (synthetic raw ViT-B at 518^2: token diversity 0.18 on an all-zero
+        image, 0.11 on a noise image; profiles/r05_aa_*), the input does.
+        flat -- tap_div < lad["div"] or in_div < lad["div_in"].
+        The sizes are ``eng``'s (whose buffers are read); the ladder and the final activation are this engine's -- the third-rung engine is built from the same
+        module and has no ladder of its own (and calibrate() switches the activation of both)."""
         lad = self.ladder
-        if lad is None:
-            return out
-        if torch.cuda.is_current_stream_capturing():
-            return out
-        B, H, W = out.shape[0], out.shape[-2], out.shape[-1]
-        if ws is None:
-            ws = self.workspace(B, H, W, out.device)
-        D = self.w.dim
-        # r: the sensitivity of the metric to a logit error, from the output itself -- sum s(1-s) / sum s behind a sigmoid, (positive outputs) / sum out behind a
-        # ReLU (round 6: a clipped pixel carries no error; a map that is mostly clipped with the rest just above the kink has a small denominator), N / sum |out|
-        # for bare logits.  Thresholds: lad["r"] (second rung: head re-run; sigmoid policy) and lad["r3"] (third rung), both CALIBRATED per checkpoint (calibrate()).
+        B, D = out.shape[0], eng.w.dim
         has_r = "r" in lad or "r3" in lad
         has_div = lad.get("div", 0.0) > 0.0
+        has_in = ws.stat_in is not None
         if has_r:
-            k_depth_stats(out, ws.stat_sums, self.final_act)
+            self._depth_sums(out, ws.stat_sums)
         if has_div:
             k_token_diversity(ws.taps[3], ws.taps[3].shape[1], B, ws.ph * ws.pw, D, ws.stat_div)
-        if ws.stat_in is not None:
-            k_token_diversity(ws.a_pe, ws.a_pe.shape[1], B, ws.ph * ws.pw, self.w.pe_seg, ws.stat_in)
-        host = ws.stat_buf.cpu().double()                       # the forward's one synchronisation: (8 + D / 64 + patch width / 64) x 2 floats per image
+        if has_in:
+            k_token_diversity(ws.a_pe, ws.a_pe.shape[1], B, ws.ph * ws.pw, eng.w.pe_seg, ws.stat_in)
+        host = ws.stat_buf.cpu().double()
         nst, ndv = B * STAT_CHUNKS * 2, B * ((D + 63) // 64) * 2
-        st, dv = host[:nst].view(B, STAT_CHUNKS, 2).sum(1), host[nst:nst + ndv].view(B, -1, 2).sum(1)
-        ratio = st[:, 1] / st[:, 0].clamp_min(1e-300) if has_r else torch.zeros(B, dtype=torch.float64)
-        self.last_ratio = ratio if has_r else None
+        st = host[:nst].view(B, STAT_CHUNKS, 2).sum(1)
+        r = st[:, 1] / st[:, 0].clamp_min(1e-300) if has_r else torch.zeros(B, dtype=torch.float64)
         flat = torch.zeros(B, dtype=torch.bool)
-        self.last_diversity = None
+        tap_div = in_div = None
         if has_div:
-            self.last_diversity = dv[:, 0] / dv[:, 1].clamp_min(1e-300)
-            flat = self.last_diversity < lad["div"]
-        if ws.stat_in is not None:
-            # input-side trigger: the patches of the image are all alike (variance over patches below 1e-4 of their mean square) -- the raw models' last tap does not
-            # tell (synthetic raw ViT-B at 518^2: token diversity 0.18 on an all-zero image, 0.11 on a noise image; profiles/r05_aa_*), the input does
+            dv = host[nst:nst + ndv].view(B, -1, 2).sum(1)
+            tap_div = dv[:, 0] / dv[:, 1].clamp_min(1e-300)
+            flat = tap_div < lad["div"]
+        if has_in:      # every patch of the image alike: variance over patches below 1e-4 of their mean square
             di = host[nst + ndv:].view(B, -1, 2).sum(1)
-            self.last_input_diversity = di[:, 0] / di[:, 1].clamp_min(1e-300)
-            flat = flat | (self.last_input_diversity < lad.get("div_in", 1e-4))
-        trigger = ((ratio > lad["r"]) if ("r" in lad and "make" in lad) else torch.zeros_like(flat)) | (flat if "make" in lad else torch.zeros_like(flat))
-        # constant / checkerboard inputs take the third rung too: their rounding errors add coherently in the ENCODER as well (ViT-B, all-zero image at 126 x 154:
-        # 8.5e-4 with the head in split precision, 2.3e-4 with everything), and what a degenerate input costs does not matter
-        top = (((ratio > lad["r3"]) if "r3" in lad else torch.zeros_like(flat)) | flat) if ("make3" in lad and x is not None) else torch.zeros_like(trigger)
-        if not self._warned and bool((trigger | top).any()):
+            in_div = di[:, 0] / di[:, 1].clamp_min(1e-300)
+            flat = flat | (in_div < lad.get("div_in", 1e-4))
+        return r, flat, tap_div, in_div
+
+    def _depth_sums(self, out: torch.Tensor, sums: torch.Tensor):
+        """The one launch of ada_depth_stats_fwd for the ladder: (sum |f|, sum w) of every image of ``out`` in STAT_CHUNKS chunks."""
+        k_depth_stats(out, sums, self.final_act)
+
+    def _ratio_of(self, out: torch.Tensor) -> torch.Tensor:
+        """r of every image of ``out`` (see _image_stats) -- one reduction + one host read.  For a head run on a SUBSET of a workspace's images (the first rung
+        behind the second), whose ``out`` has fewer rows than the workspace's statistics buffer."""
+        sums = torch.empty(out.shape[0], STAT_CHUNKS, 2, dtype=torch.float32, device=out.device)
+        self._depth_sums(out, sums)
+        st = sums.cpu().double().sum(1)
+        return st[:, 1] / st[:, 0].clamp_min(1e-300)
+
+    def _ladder(self, x: torch.Tensor, guide: Optional[torch.Tensor], norm: Optional[bool], first=None) -> torch.Tensor:
+        """One forward through the precision ladder.  FIRST RUNG: this engine's own weights -- for the sigmoid ViT-B / ViT-L models the DPT
+        head on single fp16 operands, counting on the sigmoid to compress the logit error it leaves (~1.2e-3 mean absolute); in the metric that error arrives
+        multiplied by the image's r (_image_stats).  SECOND RUNG (lad["make"], thresholded by lad["r"]): the HEAD ONLY (27 % of the FLOPs) re-run in split precision
+        from the four taps, which this engine keeps [hi | lo] for the purpose.  THIRD RUNG (lad["make3"], lad["r3"], and every flat image): the whole forward,
+        encoder blocks and head, in split precision -- at the bottom of the range the second rung's own logit error (the ENCODER's operand rounding) is what shows,
+        and on constant / checkerboard inputs the rounding errors add coherently in the encoder as well.  Thresholds are calibrated per checkpoint (calibrate()).
+
+        The rung of an image is a pure function of its own results (hip_ext.ladder.ladder_decide): deterministic, independent of the rest of the batch.  Which rung
+        runs FIRST is a matter of cost alone: the one most images of this engine's previous call ended on (next_start_rung; a stream of low-mean images does not pay
+        12 ms of first-rung head per bs=32 step for nothing), whose r decides for every image outside a guard band around the thresholds; for the others the first
+        rung is run and its r decides, exactly as if it had run first.  Every image carries the output of its rung, bit for bit, in every order.
+        ``first``: the (workspace, output) of a first-rung run a graph replay has already made (_GraphedForward's ``post`` hook).  Off under stream capture (a
+        caller's own HIP graph cannot hold a data-dependent branch): the first rung's output is returned, no counter moves."""
+        lad = self.ladder
+        capturing = torch.cuda.is_current_stream_capturing()
+        start = 1
+        if lad is not None and first is None and LADDER_STICKY and not capturing:
+            if self._start_rung == 3 and "make3" in lad and lad.get("r3", float("inf")) < float("inf"):
+                start = 3
+            elif self._start_rung == 2 and "make" in lad:
+                start = 2
+        # 1. the start rung for the whole batch
+        if start == 1:
+            eng = self
+            ws, out = first if first is not None else (None, self._forward(x, guide, norm))
+            if lad is None or capturing:
+                return out
+            if ws is None:
+                ws = self.workspace(out.shape[0], out.shape[-2], out.shape[-1], out.device)
+        elif start == 2:
+            eng = self
+            ws = self._forward(x, guide, norm, head=False)
+            out = self._head_for(ws, ws.B, None, self._second_weights())
+        else:
+            eng = self._third_engine()
+            out = eng.forward(x, guide, norm)
+            ws = self._third_workspace(eng, out)
+        B, dev = out.shape[0], out.device
+
+        def rows(t, idx):
+            return None if t is None else t.index_select(0, idx.to(dev))
+        # 2. its statistics decide every image they can
+        ratio, flat, tap_div, in_div = self._image_stats(eng, ws, out)
+        rung = ladder_decide(ratio, flat, lad, start, LADDER_GUARD)
+        # 3. the first rung for the others.  idx1 = the batch rows of the images of the first-rung run, ASCENDING, so that row j of that run (out1, and the taps
+        #    in ws1) is image idx1[j]: everything for start rung 1; the undecided images otherwise (start rung 2: their taps are rows idx1 of ws itself)
+        idx1, ws1, out1 = torch.arange(B), ws, out
+        if start != 1:
+            idx1, out1 = torch.nonzero(rung == 0).flatten(), None
+        if start != 1 and idx1.numel() > 0:
+            if start == 2:      # the first-rung head over the same taps; not flat, or ladder_decide had decided them
+                out1 = self._head_for(ws, B, None if idx1.numel() == B else idx1, self.w)
+                r1, flat1 = self._ratio_of(out1), torch.zeros(idx1.numel(), dtype=torch.bool)
+            else:               # a plain forward of the subset; r AND the diversities are those of this run
+                out1 = self._forward(rows(x, idx1), rows(guide, idx1), norm)
+                ws1 = self.workspace(out1.shape[0], out1.shape[-2], out1.shape[-1], dev)
+                r1, flat1, d1, di1 = self._image_stats(self, ws1, out1)
+                in_div[idx1] = di1
+                if tap_div is not None:
+                    tap_div[idx1] = d1
+            ratio[idx1] = r1
+            rung[idx1] = ladder_decide(r1, flat1, lad, 1, LADDER_GUARD)
+        # 4. every image from the output of its rung, running only what is not in hand
+        #    (order as before: third rung, second, first).  `have`: the start rung's output IS the image's; `pos`: batch row -> row of the first-rung run
+        have = rung == start
+        if start == 3:
+            have[idx1] = False      # (run again on the subset, as the first-rung-first order does: the two runs' bits have not been compared)
+        pos = torch.zeros(B, dtype=torch.int64)
+        pos[idx1] = torch.arange(idx1.numel())
+        need1, need2, need3 = (torch.nonzero((rung == k) & ~have).flatten() for k in (1, 2, 3))
+        if need3.numel() == B:
+            out = self._third_engine().forward(x, guide, norm)
+        elif need3.numel() > 0:
+            out.index_copy_(0, need3.to(dev), self._third_engine().forward(rows(x, need3), rows(guide, need3), norm))
+        if need2.numel() > 0:       # the head re-run from the taps of the first-rung run (never from start rung 2: its rung-2 images are in hand)
+            assert start != 2
+            hi = self._head_for(ws1, ws1.B, None if need2.numel() == ws1.B else pos[need2], self._second_weights())
+            out = hi if need2.numel() == B else out.index_copy_(0, need2.to(dev), hi)
+        if need1.numel() > 0:
+            out = out1 if need1.numel() == B else out.index_copy_(0, need1.to(dev), rows(out1, pos[need1]))
+        # 5. the books
+        n2, n3 = rung_counts(rung)
+        self.escalated += n2
+        self.escalated3 += n3
+        self.second_rung_first_calls += int(start == 2)
+        self.third_rung_first_calls += int(start == 3)
+        self._start_rung = next_start_rung(rung, "make" in lad)
+        self.last_ratio = ratio if ("r" in lad or "r3" in lad) else None      # per image: r1 where the first rung ran for it, else the start rung's r
+        self.last_diversity, self.last_input_diversity = tap_div, in_div      # always B long: of the rung that ran first for the image
+        if n2 and not self._warned:
             self._warned = True
             import warnings
-            warnings.warn(f"precision ladder: {int((trigger | top).sum())} of {B} image(s) re-run in split precision (second rung: head only; third: whole forward) -- "
+            warnings.warn(f"precision ladder: {n2} of {B} image(s) re-run in split precision (second rung: head only; third: whole forward; {n3} on the third) -- "
                           f"r up to {float(ratio.max()):.3g} against thresholds {lad.get('r')} / {lad.get('r3')}; counted in DepthEngine.escalated / escalated3 "
                           "(this message appears once per engine; module.precision_ladder = False switches the ladder off)")
-        # which rung the NEXT call starts on (_run_ladder): the one most of this call's images ended on
-        self._start_rung = 3 if 2 * int(top.sum()) > B else (2 if ("make" in lad and 2 * int((trigger & ~top).sum()) > B) else 1)
-        idx3 = torch.nonzero(top).flatten()
-        if idx3.numel() > 0:      # third rung: the whole forward in split precision for these images, straight from the inputs
-            if self._eng3 is None:
-                self._eng3 = lad["make3"]()
-            if idx3.numel() == B:
-                self.escalated += B
-                self.escalated3 += B
-                return self._eng3.forward(x, guide, norm)
-            sel3 = idx3.to(out.device)
-            out3 = self._eng3.forward(x.index_select(0, sel3), None if guide is None else guide.index_select(0, sel3), norm)
-            out.index_copy_(0, sel3, out3)
-            self.escalated += int(idx3.numel())
-            self.escalated3 += int(idx3.numel())
-        idx = torch.nonzero(trigger & ~top).flatten()
-        if idx.numel() == 0:
-            return out
-        if self._w_hi is None:
-            self._w_hi = lad["make"]()
-        Be = int(idx.numel())
-        hi = self._head_for(ws, B, None if Be == B else idx, self._w_hi)
-        if Be == B:
-            out = hi
-        else:
-            out.index_copy_(0, idx.to(out.device), hi)
-        self.escalated += Be
         return out
 
     def _head_for(self, ws: Workspace, B: int, idx: Optional[torch.Tensor], w: PackedWeights) -> torch.Tensor:
@@ -973,147 +997,6 @@ class DepthEngine:
             if own_cls is not None:
                 ws2.cls_op = own_cls
 
-    def _run_ladder(self, x: torch.Tensor, guide: Optional[torch.Tensor], norm: Optional[bool]) -> torch.Tensor:
-        """First rung + the ladder's check -- or, when most images of this engine's PREVIOUS call left the first rung (maps near 0: a stream of such images pays
-        12 ms of first-rung head per bs=32 step for nothing), the second rung first (_second_rung_first).  Which head runs first changes what a call costs, never
-        what it returns: every image carries exactly the output of the rung the first-rung-first order assigns it."""
-        lad = self.ladder
-        if lad is None or not LADDER_STICKY or self._start_rung == 1 or torch.cuda.is_current_stream_capturing():
-            return self._escalate(None, self._forward(x, guide, norm), x, guide, norm)
-        if self._start_rung == 3 and "make3" in lad and lad.get("r3", float("inf")) < float("inf"):
-            return self._third_rung_first(x, guide, norm)
-        if self._start_rung == 2 and "make" in lad:
-            return self._second_rung_first(x, guide, norm)
-        return self._escalate(None, self._forward(x, guide, norm), x, guide, norm)
-
-    def _third_rung_first(self, x: torch.Tensor, guide: Optional[torch.Tensor], norm: Optional[bool]) -> torch.Tensor:
-        """Most images of the previous call ended on the THIRD rung (a checkpoint / operating point whose first rung never suffices: the bf16 build, raw maps that are
-        mostly clipped): the everything-split engine runs first for the whole batch and r is read from ITS output.  Images with r3 > threshold (1 + g), or flat
-        inputs, keep it -- exactly what the first-rung-first order returns for them; every other image goes through the ordinary order (first rung, then whatever its
-        own r1 says).  A third-rung stream costs the third rung, not the sum of the rungs in front of it."""
-        lad = self.ladder
-        if self._eng3 is None:
-            self._eng3 = lad["make3"]()
-        eng3 = self._eng3
-        out = eng3.forward(x, guide, norm)
-        B, H, W = out.shape[0], out.shape[-2], out.shape[-1]
-        ws3 = eng3.workspace(B, H, W, out.device)
-        r3v = self._ratio_of(out)
-        D = self.w.dim
-        flat = torch.zeros(B, dtype=torch.bool)
-        stat = torch.zeros(B * max((D + 63) // 64, ws3.a_pe.shape[1] // 128 + 1) * 2, dtype=torch.float32, device=out.device)
-        if lad.get("div", 0.0) > 0.0:
-            G = (D + 63) // 64
-            k_token_diversity(ws3.taps[3], ws3.taps[3].shape[1], B, ws3.ph * ws3.pw, D, stat[:B * G * 2].view(B, G, 2))
-            dv = stat[:B * G * 2].view(B, G, 2).cpu().double().sum(1)
-            self.last_diversity = dv[:, 0] / dv[:, 1].clamp_min(1e-300)
-            flat = self.last_diversity < lad["div"]
-        Gi = eng3.w.pe_seg // 64
-        k_token_diversity(ws3.a_pe, ws3.a_pe.shape[1], B, ws3.ph * ws3.pw, eng3.w.pe_seg, stat[:B * Gi * 2].view(B, Gi, 2))
-        di = stat[:B * Gi * 2].view(B, Gi, 2).cpu().double().sum(1)
-        self.last_input_diversity = di[:, 0] / di[:, 1].clamp_min(1e-300)
-        flat = flat | (self.last_input_diversity < lad.get("div_in", 1e-4))
-        sure = flat | (r3v > lad["r3"] * (1.0 + LADDER_GUARD))
-        ratio = r3v.clone()
-        n3 = int(sure.sum())
-        rest = torch.nonzero(~sure).flatten()
-        rung_rest = None
-        if rest.numel() > 0:
-            sel = rest.to(out.device)
-            xs, gs = x.index_select(0, sel), (None if guide is None else guide.index_select(0, sel))
-            e0, e3 = self.escalated, self.escalated3
-            sub = self._escalate(None, self._forward(xs, gs, norm), xs, gs, norm)
-            out.index_copy_(0, sel, sub)
-            ratio[rest] = self.last_ratio if self.last_ratio is not None else r3v[rest]
-            rung_rest = (self.escalated - e0, self.escalated3 - e3)
-        self.last_ratio = ratio
-        self.escalated += n3
-        self.escalated3 += n3
-        self.third_rung_first_calls += 1
-        on3 = n3 + (rung_rest[1] if rung_rest else 0)
-        on2 = (rung_rest[0] - rung_rest[1]) if rung_rest else 0
-        self._start_rung = 3 if 2 * on3 > B else (2 if ("make" in lad and 2 * on2 > B) else 1)
-        return out
-
-    def _ratio_of(self, out: torch.Tensor) -> torch.Tensor:
-        """r of every image of ``out`` (see _escalate) -- one reduction + one host read."""
-        sums = torch.empty(out.shape[0], STAT_CHUNKS, 2, dtype=torch.float32, device=out.device)
-        k_depth_stats(out, sums, self.final_act)
-        st = sums.cpu().double().sum(1)
-        return st[:, 1] / st[:, 0].clamp_min(1e-300)
-
-    def _second_rung_first(self, x: torch.Tensor, guide: Optional[torch.Tensor], norm: Optional[bool]) -> torch.Tensor:
-        """Encoder -> SECOND-rung head for the whole batch -> r from its output.  The two rungs' maps differ by ~1e-3 of their logits, so r2 decides for every image
-        that is not within LADDER_GUARD of a threshold: r2 > r (1 + g) keeps the second rung's result (what the first-rung-first order would have computed for it,
-        bit for bit -- the same head over the same taps), r2 > r3 (1 + g) or a flat input goes to the third rung.  Every other image -- below the threshold, or inside a
-        guard band -- gets the FIRST-rung head run for it and is decided by its r1 exactly as _escalate decides: the output is a pure function of the image either way."""
-        lad = self.ladder
-        ws = self._forward(x, guide, norm, head=False)
-        B, H, W = ws.B, ws.H, ws.W
-        D = self.w.dim
-        if self._w_hi is None:
-            self._w_hi = lad["make"]()
-        out = self._head_for(ws, B, None, self._w_hi)
-        has_div = lad.get("div", 0.0) > 0.0
-        k_depth_stats(out, ws.stat_sums, self.final_act)
-        if has_div:
-            k_token_diversity(ws.taps[3], ws.taps[3].shape[1], B, ws.ph * ws.pw, D, ws.stat_div)
-        if ws.stat_in is not None:
-            k_token_diversity(ws.a_pe, ws.a_pe.shape[1], B, ws.ph * ws.pw, self.w.pe_seg, ws.stat_in)
-        host = ws.stat_buf.cpu().double()
-        nst, ndv = B * STAT_CHUNKS * 2, B * ((D + 63) // 64) * 2
-        st, dv = host[:nst].view(B, STAT_CHUNKS, 2).sum(1), host[nst:nst + ndv].view(B, -1, 2).sum(1)
-        r2 = st[:, 1] / st[:, 0].clamp_min(1e-300)
-        flat = torch.zeros(B, dtype=torch.bool)
-        self.last_diversity = None
-        if has_div:
-            self.last_diversity = dv[:, 0] / dv[:, 1].clamp_min(1e-300)
-            flat = self.last_diversity < lad["div"]
-        if ws.stat_in is not None:
-            di = host[nst + ndv:].view(B, -1, 2).sum(1)
-            self.last_input_diversity = di[:, 0] / di[:, 1].clamp_min(1e-300)
-            flat = flat | (self.last_input_diversity < lad.get("div_in", 1e-4))
-        g = LADDER_GUARD
-        thr, thr3 = lad["r"], lad.get("r3", float("inf"))
-        has3 = "make3" in lad
-        near3 = ((r2 / thr3 - 1.0).abs() <= g) if (has3 and thr3 < float("inf")) else torch.zeros_like(flat)
-        need1 = ~flat & ((r2 <= thr * (1.0 + g)) | near3)          # the first rung decides (and, below the threshold, IS the result)
-        rung = torch.full((B,), 2, dtype=torch.int64)
-        if has3:
-            rung[flat | (r2 > thr3 * (1.0 + g))] = 3
-        ratio = r2.clone()
-        idx1 = torch.nonzero(need1).flatten()
-        out1 = None
-        if idx1.numel() > 0:
-            out1 = self._head_for(ws, B, None if idx1.numel() == B else idx1, self.w)
-            r1 = self._ratio_of(out1)
-            ratio[idx1] = r1
-            rung[idx1] = torch.where((r1 > thr3) & has3, torch.tensor(3), torch.where(r1 > thr, torch.tensor(2), torch.tensor(1)))
-        self.last_ratio = ratio
-        sel1 = torch.nonzero(rung == 1).flatten()
-        if sel1.numel() > 0:      # the first rung's maps go where the first rung stands
-            pos = {int(v): j for j, v in enumerate(idx1.tolist())}
-            src = torch.tensor([pos[int(v)] for v in sel1.tolist()], device=out.device)
-            out.index_copy_(0, sel1.to(out.device), out1.index_select(0, src))
-        sel3 = torch.nonzero(rung == 3).flatten()
-        if sel3.numel() > 0:
-            if self._eng3 is None:
-                self._eng3 = lad["make3"]()
-            s3 = sel3.to(out.device)
-            out3 = self._eng3.forward(x.index_select(0, s3), None if guide is None else guide.index_select(0, s3), norm)
-            out.index_copy_(0, s3, out3)
-        n2 = int((rung >= 2).sum())
-        self.escalated += n2
-        self.escalated3 += int(sel3.numel())
-        self.second_rung_first_calls += 1
-        self._start_rung = 3 if 2 * int((rung == 3).sum()) > B else (2 if 2 * int((rung == 2).sum()) > B else 1)
-        if not self._warned and n2:
-            self._warned = True
-            import warnings
-            warnings.warn(f"precision ladder: {n2} of {B} image(s) on the second / third rung (r up to {float(ratio.max()):.3g} against thresholds {thr} / {lad.get('r3')}); "
-                          "counted in DepthEngine.escalated / escalated3 (this message appears once per engine)")
-        return out
-
     def calibrate(self, x: torch.Tensor, guide: Optional[torch.Tensor], budget: float = 9e-4, safety: float = 1.1, flat_index: Optional[int] = None,
                   rule: str = "cross") -> dict:
         """Self-calibration of the ladder's thresholds for THIS checkpoint, on the device, with no oracle (round 6; round 5's thresholds were ~12 constants fitted
@@ -1121,7 +1004,7 @@ class DepthEngine:
         (head re-run from the first rung's taps, where the policy has one) and through the third-rung engine -- every encoder block and the whole head in split
         precision, 1.6-3.7e-4 from the reference where it was measured -- with the final activation switched OFF, i.e. as logits z1, z2, z3.  For a grid of bias
         shifts d (the final bias is added in fp32: moving it moves the map's operating point and nothing else) the metric of rung k against the third,
-        e = mean|f(z_k + d) - f(z_3 + d)| / mean f(z_3 + d), is known together with the image's r (see _escalate); e / r is the rung's sensitivity-normalised
+        e = mean|f(z_k + d) - f(z_3 + d)| / mean f(z_3 + d), is known together with the image's r (see _image_stats); e / r is the rung's sensitivity-normalised
         logit error eps_k.  Rule "cross" (default): a rung is left at the smallest r at which any calibration point has safety * e > budget; rule "global":
         at budget / (safety * max eps_k) -- the worst eps anywhere on the grid (round 5's hand-fitted constants, 0.42 / 0.45, are what "global" returns for the
         synthetic fills they were fitted on at budget 9e-4).  r from rung 1, r3 from rung 2 (heads without a second rung: r3 from rung 1).  ``flat_index``: a
@@ -1131,9 +1014,7 @@ class DepthEngine:
         if lad is None or "make3" not in lad:
             raise HipExtError("calibrate: this engine has no precision ladder")
         B, H, W = x.shape[0], x.shape[-2], x.shape[-1]
-        if self._eng3 is None:
-            self._eng3 = lad["make3"]()
-        eng3 = self._eng3
+        eng3 = self._third_engine()
         act = self.final_act
         keep = (self.final_act, eng3.final_act)
         z2 = None
@@ -1145,13 +1026,12 @@ class DepthEngine:
             dv = ws.stat_div.double().sum(1)
             tap_div = (dv[:, 0] / dv[:, 1].clamp_min(1e-300)).cpu()
             if "make" in lad:
-                if self._w_hi is None:
-                    self._w_hi = lad["make"]()
-                ws2 = Workspace(self._w_hi, B, H, W, x.device, head_only=True)
+                w_hi = self._second_weights()
+                ws2 = Workspace(w_hi, B, H, W, x.device, head_only=True)
                 ws2.taps = ws.taps
                 if getattr(ws2, "cls_op", None) is not None:
                     ws2.cls_op = ws.cls_op
-                z2 = self._head(ws2, B, self._w_hi)
+                z2 = self._head(ws2, B, w_hi)
             z3 = eng3._forward(x, guide, True)
         finally:
             self.final_act, eng3.final_act = keep
@@ -1165,7 +1045,7 @@ class DepthEngine:
         return res
 
     def _forward(self, x: torch.Tensor, guide: Optional[torch.Tensor], norm: Optional[bool] = None, head: bool = True):
-        """The first rung: encoder + DPT head -> depth map.  ``head=False``: the encoder only -- returns the Workspace holding the four taps (_second_rung_first)."""
+        """The first rung: encoder + DPT head -> depth map.  ``head=False``: the encoder only -- returns the Workspace holding the four taps (_ladder, second rung first)."""
         w = self.w
         if not x.is_cuda:
             raise HipExtError("DepthEngine.forward: input must live on a HIP device (no CPU fallback in the product path)")

@@ -193,7 +193,7 @@ def _encoder_split_policy(mode, encoder, final_act):
     return int(mode)
 
 
-# Precision ladder of the sigmoid heads ("auto" policy only; hip_ext.engine.DepthEngine._escalate).  The single-precision head leaves a mean absolute
+# Precision ladder of the sigmoid heads ("auto" policy only; hip_ext.engine.DepthEngine._ladder, rule table hip_ext.ladder.ladder_decide).  The single-precision head leaves a mean absolute
 # LOGIT error of ~1.2e-3 (ViT-L) that the sigmoid compresses by r = sum s (1 - s) / sum s in the north-star metric mean|a - b| / mean|b|: r is 0.3-0.5
 # for depth maps that span (0, 1) -- every centred reference fixture, the benchmarked batch -- and tends to 1 for maps concentrated near 0, where the
 # default policy measured 1.17e-3 (ViT-L, mean 0.10) ... 2.3e-3 (ViT-B, all-zero image): profiles/r04_s_sigmoid_operating_point.txt.  Images whose
@@ -321,7 +321,7 @@ class _EngineMixin:
             # is what limits parity with the fp32 reference -- the unbounded-output models (raw ReLU head, 'ssi' heads: no sigmoid
             # compresses the logit noise) and ViT-S (64-feature head: few terms per output to average the rounding over).  The
             # sigmoid ViT-B/L models -- the benchmarked configurations -- keep the single-precision head as the FIRST RUNG of a precision
-            # ladder (DepthEngine._escalate): images whose depth map sits where the sigmoid does not compress the logit error get the head re-run
+            # ladder (DepthEngine._ladder): images whose depth map sits where the sigmoid does not compress the logit error get the head re-run
             # in split precision.
             mode = getattr(self, "head_precision", "auto")
             # ONE decision for everything that touches the fp8 form on the sigmoid ViT-B / ViT-L models (with module.f8_terms = "none" / "enc"
@@ -361,7 +361,7 @@ class _EngineMixin:
                     return DepthEngine(PackedWeights(sd, encoder, guided=guided, amodal_head=amodal_head, split_head=tuple(g for g in HEAD_GROUPS if g != "projw"),
                                                      enc_split_blocks=depth, f8=f8_), final_act, norm_in)
                 # (input-side trigger only: the raw models' last tap does not tell -- synthetic raw ViT-G reads a token diversity of 0.09 on a small NOISE image)
-                # round 6: + the r trigger (sum of the metric's weights / sum |out|, hip_ext.engine._escalate) with a CALIBRATED threshold -- the un-centred raw maps of
+                # round 6: + the r trigger (sum of the metric's weights / sum |out|, hip_ext.engine.DepthEngine._image_stats) with a CALIBRATED threshold -- the un-centred raw maps of
                 # profiles/r05_ac_* (mostly clipped, the rest just above the kink) read up to 1.1e-3 under the default policy and 6.6e-4 with everything split
                 ladder = dict(div_in=_LADDER_DIV_IN, make3=everything)
             eng = DepthEngine(pw, self.depth_head.final_act, bool(getattr(self, "normalise_input", False)), ladder=ladder)

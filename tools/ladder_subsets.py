@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """What does the ladder's second rung need?  The low-mean / degenerate reference fixtures of the sigmoid heads with the DPT head's contractions in split
 precision group by group (head_precision = list, ladder off): relative L1 against the reference golden and ms per forward of a batch of 8 -- the
-cheapest subset that holds the bar is what DepthEngine._escalate should re-run.   python tools/ladder_subsets.py [fixture ...]"""
+cheapest subset that holds the bar is what DepthEngine._ladder should re-run.   python tools/ladder_subsets.py [fixture ...]"""
 import os
 import sys
 import time

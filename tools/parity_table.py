@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Reference fixtures of the sigmoid heads under the rungs of the precision ladder (GPU box; the goldens are the checker, no oracle run needed):
-per fixture the output mean, the sigmoid compression factor r = sum s(1-s) / sum s of the first-rung output (what DepthEngine._escalate thresholds),
+per fixture the output mean, the sigmoid compression factor r = sum s(1-s) / sum s of the first-rung output (what DepthEngine._ladder thresholds),
 and the relative L1 against the reference golden with
     rung 1 only (ladder off)  |  the default policy (ladder on)  |  head in split precision  |  head + leading encoder blocks in split precision.
     python tools/parity_table.py [fixture ...]        (default: every sigmoid ViT-B / ViT-L fixture)"""
