@@ -2,6 +2,9 @@
 // RAW/util/transform.py:5-158).  The reference prepares a decoded photo with OpenCV on the host: BGR -> RGB, / 255 (float64),
 // cv2.resize INTER_CUBIC to the network size, ImageNet normalisation; after the forward it resizes the depth map back to the photo
 // with F.interpolate(bilinear, align_corners=True).  Neither kernel is on the benchmark path: each is one memory-bound pass.
+// The second half of the file is the host preparation of the two-model infer.py on the device (reference infer.py:17-18, 77, 83-91, 113): the
+// photo resized twice (cv2's 8-bit INTER_LINEAR for the base network, ATen's nearest for the amodal one) in one pass, the amodal masks, and the
+// cv2 INTER_NEAREST resize of a result back to the photo.  Same launch shape, same rule: one thread per output pixel, no scratch.
 #include "ada_common.h"
 
 namespace {
@@ -101,6 +104,126 @@ __global__ __launch_bounds__(256) void depth_resize_kernel(DepthResizeArgs a) {
     a.out[((long)b * a.ho + y) * a.wo + x] = h0 * (w0 * r0[x0] + w1 * r0[x1]) + h1 * (w0 * r1[x0] + w1 * r1[x1]);
 }
 
+// One axis of cv2.resize's 8-bit INTER_LINEAR (imgproc/src/resize.cpp, resizeGeneric_ with HResizeLinear / VResizeLinear<uchar, int, short>):
+// fx = (float)((d + 0.5) * scale - 0.5) in double, s = floor(fx), fx -= s; at the borders the tap is pinned and fx = 0; the two coefficients are
+// shorts on an 11-bit scale, cvRound (half to even) of the fp32 products.  Returns s; the second tap is min(s + 1, n_in - 1).
+ADA_DEV int linear_src(int d, double scale, int n_in, int& a0, int& a1) {
+#pragma clang fp contract(off)
+    float f = (float)(((double)d + 0.5) * scale - 0.5);
+    int s = (int)__builtin_floorf(f);
+    f -= (float)s;
+    if (s < 0) { s = 0; f = 0.f; }
+    if (s >= n_in - 1) { s = n_in - 1; f = 0.f; }
+    a0 = (int)__builtin_rintf((1.f - f) * 2048.f);
+    a1 = (int)__builtin_rintf(f * 2048.f);
+    return s;
+}
+
+// ATen's nearest rule (UpSample.h nearest_idx): scale = (float)n_in / n_out, src = min((int)floorf(dst * scale), n_in - 1), all in fp32
+ADA_DEV int aten_nearest(int d, float scale, int n_in) {
+    const int s = (int)__builtin_floorf((float)d * scale);
+    return s < n_in - 1 ? s : n_in - 1;
+}
+
+struct PhotoArgs {
+    const uint8_t* src;
+    long pitch;              // bytes between rows
+    int hi, wi, cn;          // cn = 3 (BGR) or 4 (BGRA, alpha ignored)
+    int ho, wo;
+    double sy, sx;           // 1 / ((double)ho / hi), 1 / ((double)wo / wi): cv2's scale_y / scale_x
+    float ny, nx;            // (float)hi / ho, (float)wi / wo: ATen's nearest scales
+    int area;                // hi == 2 ho && wi == 2 wo: cv2 turns INTER_LINEAR into the 2 x 2 area mean
+    float* raw;              // [3, ho, wo] or NULL
+    float* near;             // [3, ho, wo] or NULL
+};
+
+// block (64, 4) as image_prep_kernel: one output pixel per thread, the three channels of both planes; a wave covers 64 consecutive x of one
+// output row, so it shares its two source rows and each plane store is one contiguous 256-byte segment.  The channel order of the source
+// is KEPT (plane c = byte c of a pixel): the reference feeds B, G, R planes to both networks on this path (infer.py:17-18, 83).
+// v / 255.f is IEEE division (the build does not relax it): the correctly rounded quotient torch computes for `tensor / 255`.
+__global__ __launch_bounds__(256) void photo_prep_kernel(PhotoArgs a) {
+    const int dx = blockIdx.x * 64 + threadIdx.x;
+    const int dy = blockIdx.y * 4 + threadIdx.y;
+    if (dx >= a.wo || dy >= a.ho) return;
+    const long plane = (long)a.ho * a.wo;
+    const long o = (long)dy * a.wo + dx;
+    if (a.raw) {
+        int v[3];
+        if (a.area) {
+            const uint8_t* r0 = a.src + (long)(2 * dy) * a.pitch + (long)(2 * dx) * a.cn;
+            const uint8_t* r1 = r0 + a.pitch;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = ((int)r0[c] + (int)r0[a.cn + c] + (int)r1[c] + (int)r1[a.cn + c] + 2) >> 2;
+        } else {
+            int ax0, ax1, ay0, ay1;
+            const int x0 = linear_src(dx, a.sx, a.wi, ax0, ax1);
+            const int y0 = linear_src(dy, a.sy, a.hi, ay0, ay1);
+            const int x1 = x0 + 1 < a.wi ? x0 + 1 : a.wi - 1;
+            const int y1 = y0 + 1 < a.hi ? y0 + 1 : a.hi - 1;
+            const uint8_t* r0 = a.src + (long)y0 * a.pitch;
+            const uint8_t* r1 = a.src + (long)y1 * a.pitch;
+            const long o0 = (long)x0 * a.cn, o1 = (long)x1 * a.cn;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                // horizontal pass on the two source rows, then cv2's vertical pass with its intermediate shifts; all int32:
+                // 255 * 2048 >> 4 = 32640 and 32640 * 2048 < 2^31
+                const int h0 = (int)r0[o0 + c] * ax0 + (int)r0[o1 + c] * ax1;
+                const int h1 = (int)r1[o0 + c] * ax0 + (int)r1[o1 + c] * ax1;
+                const int t = (((ay0 * (h0 >> 4)) >> 16) + ((ay1 * (h1 >> 4)) >> 16) + 2) >> 2;
+                v[c] = t > 255 ? 255 : t;   // saturate_cast<uchar>; never negative
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.raw[c * plane + o] = (float)v[c] / 255.f;
+    }
+    if (a.near) {
+        const uint8_t* p = a.src + (long)aten_nearest(dy, a.ny, a.hi) * a.pitch + (long)aten_nearest(dx, a.nx, a.wi) * a.cn;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.near[c * plane + o] = (float)p[c] / 255.f;
+    }
+}
+
+struct MaskArgs {
+    const uint8_t* src;
+    long pitch, istride;     // bytes between rows / masks
+    int hi, wi, ho, wo;
+    float ny, nx;            // ATen's nearest scales
+    float* out01;            // [K, 1, ho, wo]
+    float* out_pm1;          // [K, 1, ho, wo] or NULL
+};
+
+// block (64, 4), grid z = mask: m = src != 0 at ATen's nearest source pixel; out01 = m, out_pm1 = 2 m - 1
+__global__ __launch_bounds__(256) void mask_prep_kernel(MaskArgs a) {
+    const int dx = blockIdx.x * 64 + threadIdx.x;
+    const int dy = blockIdx.y * 4 + threadIdx.y;
+    const int k = blockIdx.z;
+    if (dx >= a.wo || dy >= a.ho) return;
+    const uint8_t s = a.src[(long)k * a.istride + (long)aten_nearest(dy, a.ny, a.hi) * a.pitch + aten_nearest(dx, a.nx, a.wi)];
+    const long o = ((long)k * a.ho + dy) * a.wo + dx;
+    a.out01[o] = s ? 1.f : 0.f;
+    if (a.out_pm1) a.out_pm1[o] = s ? 1.f : -1.f;
+}
+
+struct NearestArgs {
+    const float* in;
+    float* out;
+    int hi, wi, ho, wo;
+    double ify, ifx;         // 1 / ((double)ho / hi), 1 / ((double)wo / wi)
+};
+
+// cv2.resize(INTER_NEAREST) (resizeNN): sx = min((int)floor(dx * ifx), wi - 1) in double, the same for y.  Block (64, 4), grid z = image.
+__global__ __launch_bounds__(256) void nearest_resize_kernel(NearestArgs a) {
+    const int dx = blockIdx.x * 64 + threadIdx.x;
+    const int dy = blockIdx.y * 4 + threadIdx.y;
+    const int b = blockIdx.z;
+    if (dx >= a.wo || dy >= a.ho) return;
+    int sx = (int)__builtin_floor((double)dx * a.ifx);
+    int sy = (int)__builtin_floor((double)dy * a.ify);
+    sx = sx < a.wi - 1 ? sx : a.wi - 1;
+    sy = sy < a.hi - 1 ? sy : a.hi - 1;
+    a.out[((long)b * a.ho + dy) * a.wo + dx] = a.in[((long)b * a.hi + sy) * a.wi + sx];
+}
+
 }  // namespace
 
 extern "C" int ada_image_prep_fwd(const uint8_t* src, int32_t batch, int32_t hi, int32_t wi, int32_t channels, int64_t row_pitch_bytes,
@@ -137,4 +260,56 @@ extern "C" int ada_depth_resize_fwd(const float* in, int32_t batch, int32_t hi, 
     hipLaunchKernelGGL(depth_resize_kernel, dim3((unsigned)((wo + 63) / 64), (unsigned)((ho + 3) / 4), (unsigned)batch), dim3(64, 4), 0,
                        (hipStream_t)stream, a);
     return ada_check_launch("ada_depth_resize_fwd");
+}
+
+extern "C" int ada_photo_prep_fwd(const uint8_t* src, int32_t hi, int32_t wi, int32_t channels, int64_t row_pitch_bytes, int32_t ho, int32_t wo,
+                                  float* raw_out, float* near_out, void* stream) {
+    ADA_REQUIRE(src && (raw_out || near_out), ADA_EINVAL, "ada_photo_prep_fwd: null pointer");
+    ADA_REQUIRE(hi > 0 && wi > 0 && ho > 0 && wo > 0, ADA_EINVAL, "ada_photo_prep_fwd: bad shape %dx%d -> %dx%d", hi, wi, ho, wo);
+    ADA_REQUIRE(channels == 3 || channels == 4, ADA_EINVAL, "ada_photo_prep_fwd: %d channels (3 = BGR, 4 = BGRA)", channels);
+    ADA_REQUIRE(row_pitch_bytes >= (int64_t)wi * channels, ADA_EINVAL, "ada_photo_prep_fwd: row pitch %ld < %d pixels x %d bytes", (long)row_pitch_bytes, wi, channels);
+    ADA_REQUIRE((ho + 3) / 4 <= 65535, ADA_EUNSUPPORTED, "ada_photo_prep_fwd: ho exceeds the grid limit");
+    PhotoArgs a;
+    a.src = src; a.pitch = row_pitch_bytes;
+    a.hi = hi; a.wi = wi; a.cn = channels; a.ho = ho; a.wo = wo;
+    a.sy = 1.0 / ((double)ho / hi);
+    a.sx = 1.0 / ((double)wo / wi);
+    a.ny = (float)hi / (float)ho;
+    a.nx = (float)wi / (float)wo;
+    a.area = (hi == 2 * ho && wi == 2 * wo) ? 1 : 0;
+    a.raw = raw_out; a.near = near_out;
+    hipLaunchKernelGGL(photo_prep_kernel, dim3((unsigned)((wo + 63) / 64), (unsigned)((ho + 3) / 4), 1), dim3(64, 4), 0, (hipStream_t)stream, a);
+    return ada_check_launch("ada_photo_prep_fwd");
+}
+
+extern "C" int ada_mask_prep_fwd(const uint8_t* src, int32_t batch, int32_t hi, int32_t wi, int64_t row_pitch_bytes, int64_t image_stride_bytes,
+                                 int32_t ho, int32_t wo, float* out01, float* out_pm1, void* stream) {
+    ADA_REQUIRE(src && out01, ADA_EINVAL, "ada_mask_prep_fwd: null pointer");
+    ADA_REQUIRE(batch > 0 && hi > 0 && wi > 0 && ho > 0 && wo > 0, ADA_EINVAL, "ada_mask_prep_fwd: bad shape batch=%d %dx%d -> %dx%d", batch, hi, wi, ho, wo);
+    ADA_REQUIRE(row_pitch_bytes >= (int64_t)wi, ADA_EINVAL, "ada_mask_prep_fwd: row pitch %ld < %d pixels", (long)row_pitch_bytes, wi);
+    ADA_REQUIRE(batch == 1 || image_stride_bytes >= (int64_t)(hi - 1) * row_pitch_bytes + (int64_t)wi, ADA_EINVAL,
+                "ada_mask_prep_fwd: mask stride %ld overlaps the previous mask", (long)image_stride_bytes);
+    ADA_REQUIRE((ho + 3) / 4 <= 65535 && batch <= 65535, ADA_EUNSUPPORTED, "ada_mask_prep_fwd: ho / batch exceed the grid limits");
+    MaskArgs a;
+    a.src = src; a.pitch = row_pitch_bytes; a.istride = batch == 1 ? 0 : image_stride_bytes;
+    a.hi = hi; a.wi = wi; a.ho = ho; a.wo = wo;
+    a.ny = (float)hi / (float)ho;
+    a.nx = (float)wi / (float)wo;
+    a.out01 = out01; a.out_pm1 = out_pm1;
+    hipLaunchKernelGGL(mask_prep_kernel, dim3((unsigned)((wo + 63) / 64), (unsigned)((ho + 3) / 4), (unsigned)batch), dim3(64, 4), 0,
+                       (hipStream_t)stream, a);
+    return ada_check_launch("ada_mask_prep_fwd");
+}
+
+extern "C" int ada_nearest_resize_fwd(const float* in, int32_t batch, int32_t hi, int32_t wi, int32_t ho, int32_t wo, float* out, void* stream) {
+    ADA_REQUIRE(in && out, ADA_EINVAL, "ada_nearest_resize_fwd: null pointer");
+    ADA_REQUIRE(batch > 0 && hi > 0 && wi > 0 && ho > 0 && wo > 0, ADA_EINVAL, "ada_nearest_resize_fwd: bad shape batch=%d %dx%d -> %dx%d", batch, hi, wi, ho, wo);
+    ADA_REQUIRE((ho + 3) / 4 <= 65535 && batch <= 65535, ADA_EUNSUPPORTED, "ada_nearest_resize_fwd: ho / batch exceed the grid limits");
+    NearestArgs a;
+    a.in = in; a.out = out; a.hi = hi; a.wi = wi; a.ho = ho; a.wo = wo;
+    a.ify = 1.0 / ((double)ho / hi);
+    a.ifx = 1.0 / ((double)wo / wi);
+    hipLaunchKernelGGL(nearest_resize_kernel, dim3((unsigned)((wo + 63) / 64), (unsigned)((ho + 3) / 4), (unsigned)batch), dim3(64, 4), 0,
+                       (hipStream_t)stream, a);
+    return ada_check_launch("ada_nearest_resize_fwd");
 }

@@ -144,6 +144,7 @@ ADA_DEV int reflect101(int i, int n) {  // cv2 BORDER_REFLECT_101 for a radius-1
 
 // blended = mask > 0 ? amodal : base;  border = 0 < boxsum3x3(mask) < 9 (zero padded);  out = border ? blur3x3(blended) : blended
 // (reference infer.py:30-44; cv2.blur = normalised box filter with reflect-101 borders)
+// blend_aligned_kernel below is this kernel's twin (only `blended` differs): a change to the paste or blur rule here must be made there too.
 __global__ __launch_bounds__(256) void blend_kernel(const float* __restrict__ amodal, const float* __restrict__ base,
                                                     const float* __restrict__ mask, int H, int W, float* __restrict__ out) {
     const int x = blockIdx.x * 256 + threadIdx.x;
@@ -153,6 +154,46 @@ __global__ __launch_bounds__(256) void blend_kernel(const float* __restrict__ am
     auto blended = [&](int yy, int xx) {
         const long i = img + (long)yy * W + xx;
         return mask[i] > 0.0f ? amodal[i] : base[i];
+    };
+    float msum = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int yy = y + dy, xx = x + dx;
+            if (yy >= 0 && yy < H && xx >= 0 && xx < W) msum += mask[img + (long)yy * W + xx] > 0.0f ? 1.0f : 0.0f;
+        }
+    float v = blended(y, x);
+    if (msum > 0.0f && msum < 9.0f) {
+        float s = 0.0f;
+#pragma unroll
+        for (int dy = -1; dy <= 1; ++dy)
+#pragma unroll
+            for (int dx = -1; dx <= 1; ++dx) s += blended(reflect101(y + dy, H), reflect101(x + dx, W));
+        v = s / 9.0f;
+    }
+    out[img + (long)y * W + x] = v;
+}
+
+ADA_DEV float mul_then_add(float v, float scale, float shift) {
+#pragma clang fp contract(off)
+    const float p = v * scale;
+    return p + shift;
+}
+
+// blend_kernel with the demo's alignment (reference app.py:249-265): the pasted value is amodal * scale + shift of its image, the product
+// rounded before the sum as torch's `slope * x + intercept` rounds it (no FMA).  Paste and blur rule as above.
+__global__ __launch_bounds__(256) void blend_aligned_kernel(const float* __restrict__ amodal, const float* __restrict__ base,
+                                                            const float* __restrict__ mask, const float* __restrict__ scale_shift, int H, int W,
+                                                            float* __restrict__ out) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= W) return;
+    const int y = blockIdx.y, b = blockIdx.z;
+    const long img = (long)b * H * W;
+    const float sc = scale_shift[2 * b], sh = scale_shift[2 * b + 1];
+    auto blended = [&](int yy, int xx) {
+        const long i = img + (long)yy * W + xx;
+        return mask[i] > 0.0f ? mul_then_add(amodal[i], sc, sh) : base[i];
     };
     float msum = 0.0f;
 #pragma unroll
@@ -249,4 +290,17 @@ extern "C" int ada_blend_fwd(const float* amodal, const float* base, const float
     hipLaunchKernelGGL(blend_kernel, dim3((width + 255) / 256, height, batch), dim3(256), 0, (hipStream_t)stream, amodal, base, mask, height,
                        width, out);
     return ada_check_launch("ada_blend_fwd");
+}
+
+extern "C" int ada_blend_ex(const float* amodal, const float* base, const float* mask, const float* scale_shift, int32_t batch, int32_t height,
+                            int32_t width, float* out, void* stream) {
+    ADA_REQUIRE(amodal && base && mask && out, ADA_EINVAL, "ada_blend_ex: null pointer");
+    ADA_REQUIRE(batch > 0 && batch <= 65535 && height > 1 && height <= 65535 && width > 1, ADA_EINVAL, "ada_blend_ex: bad shape");
+    if (scale_shift)
+        hipLaunchKernelGGL(blend_aligned_kernel, dim3((width + 255) / 256, height, batch), dim3(256), 0, (hipStream_t)stream, amodal, base, mask,
+                           scale_shift, height, width, out);
+    else   // no alignment: the very kernel of ada_blend_fwd
+        hipLaunchKernelGGL(blend_kernel, dim3((width + 255) / 256, height, batch), dim3(256), 0, (hipStream_t)stream, amodal, base, mask, height,
+                           width, out);
+    return ada_check_launch("ada_blend_ex");
 }

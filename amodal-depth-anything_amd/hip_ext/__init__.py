@@ -18,7 +18,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 
 # --- constants mirrored from include/ada_hip.h ------------------------------------------------
-ABI_VERSION = 9
+ABI_VERSION = 10
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
 A_PLAIN, A_CONV3 = 0, 1
 MAP_PLAIN, MAP_PAD, MAP_TOKEN, MAP_SHUFFLE = 0, 1, 2, 3
@@ -30,6 +30,7 @@ EXPORTS = (
     "ada_pos_embed_resize", "ada_layernorm_fwd", "ada_layernorm_ex", "ada_patchify", "ada_write_cls", "ada_bilinear_fwd", "ada_selftest",
     "ada_minmax_fwd", "ada_depth_stats_fwd", "ada_token_diversity_fwd", "ada_normalize_fwd", "ada_blend_fwd", "ada_depth_eval_fwd", "ada_tile_blend_fwd", "ada_dpt_tail_fwd", "ada_tapsum_resize_fwd",
     "ada_image_prep_fwd", "ada_depth_resize_fwd",
+    "ada_photo_prep_fwd", "ada_mask_prep_fwd", "ada_nearest_resize_fwd", "ada_blend_ex",
     "ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_last_tile",
     "ada_debug_set_timestamps", "ada_debug_set_attention_variant", "ada_debug_count_saturated",
 )
@@ -149,6 +150,14 @@ def load(path: Optional[str] = None):
     lib.ada_image_prep_fwd.restype = c_int
     lib.ada_depth_resize_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]
     lib.ada_depth_resize_fwd.restype = c_int
+    lib.ada_photo_prep_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.ada_photo_prep_fwd.restype = c_int
+    lib.ada_mask_prep_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.ada_mask_prep_fwd.restype = c_int
+    lib.ada_nearest_resize_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]
+    lib.ada_nearest_resize_fwd.restype = c_int
+    lib.ada_blend_ex.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]
+    lib.ada_blend_ex.restype = c_int
     for name in ("ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_set_attention_variant"):
         getattr(lib, name).argtypes = [c_int]
         getattr(lib, name).restype = None
@@ -386,6 +395,15 @@ def blend(amodal, base, mask, out):
                                 B, H, W, _dev(out, "out", torch.float32), _stream()), "ada_blend_fwd")
 
 
+def blend_ex(amodal, base, mask, out, scale_shift=None):
+    """blend with an optional device fp32 [B, 2] (scale, shift): the pasted value is amodal * scale + shift (ada_blend_ex)."""
+    B, H, W = amodal.shape[0], amodal.shape[-2], amodal.shape[-1]
+    if scale_shift is not None and (tuple(scale_shift.shape) != (B, 2) or not scale_shift.is_contiguous()):
+        raise HipExtError(f"blend_ex: scale_shift must be contiguous [{B}, 2], got {tuple(scale_shift.shape)}")
+    _check(load().ada_blend_ex(_dev(amodal, "amodal", torch.float32), _dev(base, "base", torch.float32), _dev(mask, "mask", torch.float32),
+                               _opt(scale_shift, "scale_shift", torch.float32), B, H, W, _dev(out, "out", torch.float32), _stream()), "ada_blend_ex")
+
+
 def tile_blend(tiles, origin_y, origin_x, height, width, ramp, out):
     """tiles fp32 [B, T, th, tw]; origin_y / origin_x int32 [T] on the device; out fp32 [B, height, width] (ada_tile_blend_fwd)."""
     B, T, th, tw = tiles.shape
@@ -428,6 +446,47 @@ def depth_resize(inp, out):
     B, hi, wi = inp.shape
     _check(load().ada_depth_resize_fwd(_dev(inp, "in", torch.float32), B, hi, wi, out.shape[1], out.shape[2], _dev(out, "out", torch.float32), _stream()),
            "ada_depth_resize_fwd")
+
+
+def _check_src_extent(who, src, need):
+    """``src`` (uint8, possibly a strided view) must have ``need`` bytes from its first element to the end of its storage: the kernels read
+    (hi - 1) * row_pitch + a row's bytes (per image) from that pointer, whatever the view's own shape says."""
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8:
+        return      # _dev reports it
+    have = src.untyped_storage().nbytes() - src.storage_offset()
+    if min(need, have) < 0 or have < need:
+        raise HipExtError(f"{who}: src holds {have} bytes from its first pixel, the given sizes and pitches read {need}")
+
+
+def photo_prep(src, hi, wi, channels, row_pitch, ho, wo, raw_out=None, near_out=None):
+    """One uint8 BGR(A) HWC photo (rows ``row_pitch`` bytes apart) -> raw_out / near_out fp32 [3, ho, wo] (either may be None), channel order kept:
+    cv2's 8-bit INTER_LINEAR resize / 255 and ATen's nearest resize / 255 (ada_photo_prep_fwd)."""
+    for name, t in (("raw_out", raw_out), ("near_out", near_out)):
+        if t is not None and (t.numel() != 3 * ho * wo or not t.is_contiguous()):
+            raise HipExtError(f"photo_prep: {name} must be contiguous with 3 x {ho} x {wo} elements, got {tuple(t.shape)}")
+    _check_src_extent("photo_prep", src, (hi - 1) * row_pitch + wi * channels)
+    _check(load().ada_photo_prep_fwd(_dev(src, "src", torch.uint8), hi, wi, channels, row_pitch, ho, wo, _opt(raw_out, "raw_out", torch.float32),
+                                     _opt(near_out, "near_out", torch.float32), _stream()), "ada_photo_prep_fwd")
+
+
+def mask_prep(src, batch, hi, wi, row_pitch, image_stride, ho, wo, out01, out_pm1=None):
+    """uint8 masks [batch][hi][wi] (non-zero = inside) -> out01 fp32 0/1 [batch, 1, ho, wo] and optionally out_pm1 = 2 m - 1, ATen's nearest rule
+    (ada_mask_prep_fwd)."""
+    for name, t in (("out01", out01), ("out_pm1", out_pm1)):
+        if t is not None and (t.numel() != batch * ho * wo or not t.is_contiguous()):
+            raise HipExtError(f"mask_prep: {name} must be contiguous with {batch} x {ho} x {wo} elements, got {tuple(t.shape)}")
+    _check_src_extent("mask_prep", src, (batch - 1) * image_stride + (hi - 1) * row_pitch + wi)
+    _check(load().ada_mask_prep_fwd(_dev(src, "src", torch.uint8), batch, hi, wi, row_pitch, image_stride, ho, wo, _dev(out01, "out01", torch.float32),
+                                    _opt(out_pm1, "out_pm1", torch.float32), _stream()), "ada_mask_prep_fwd")
+
+
+def nearest_resize(inp, out):
+    """inp fp32 [B, hi, wi] -> out fp32 [B, ho, wo], both contiguous: cv2.resize(INTER_NEAREST)'s rule (ada_nearest_resize_fwd)."""
+    if not (inp.is_contiguous() and out.is_contiguous()) or inp.dim() != 3 or out.dim() != 3 or inp.shape[0] != out.shape[0]:
+        raise HipExtError(f"nearest_resize: contiguous [B, H, W] tensors required, got {tuple(inp.shape)} -> {tuple(out.shape)}")
+    B, hi, wi = inp.shape
+    _check(load().ada_nearest_resize_fwd(_dev(inp, "in", torch.float32), B, hi, wi, out.shape[1], out.shape[2], _dev(out, "out", torch.float32), _stream()),
+           "ada_nearest_resize_fwd")
 
 
 # --- tuning / diagnostic hooks (include/ada_hip.h, last section) ---------------------------------

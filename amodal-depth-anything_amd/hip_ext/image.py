@@ -3,13 +3,19 @@
 The reference prepares a decoded BGR photo on the host with OpenCV and numpy (RAW/util/transform.py:5-158); here the photo is copied to the
 device as uint8 and one kernel does BGR -> RGB, / 255, cv2's INTER_CUBIC resize and the ImageNet normalisation (ada_image_prep_fwd), and
 another resizes the depth map back to the photo (ada_depth_resize_fwd).  Only the network size is decided on the host.
+
+The two-model pipeline of infer.py prepares its photo differently (reference infer.py:17-18, 83-91): no BGR -> RGB, a square size x size squash,
+cv2's 8-bit INTER_LINEAR for the base network and torchvision's nearest for the amodal one, and nearest-resized masks.  photo_to_inputs,
+masks_to_tensor and resize_nearest do that on the device (ada_photo_prep_fwd, ada_mask_prep_fwd, ada_nearest_resize_fwd).
 """
 from __future__ import annotations
+
+import operator
 
 import numpy as np
 import torch
 
-from . import HipExtError, depth_resize, image_prep
+from . import HipExtError, depth_resize, image_prep, mask_prep, nearest_resize, photo_prep
 
 PIXEL_MEAN = (0.485, 0.456, 0.406)
 PIXEL_STD = (0.229, 0.224, 0.225)
@@ -49,29 +55,104 @@ def _check_image(img):
         raise ValueError(f"image: expected [h, w, 3] BGR or [h, w, 4] BGRA, got shape {tuple(img.shape)}")
 
 
+def _stage_image(img, device, who):
+    """The checked photo as a uint8 [h, w, c] tensor on ``device`` with packed pixels: numpy is copied, a device tensor is read in place at its
+    own row stride (made contiguous only when its pixels are not packed).  Returns (tensor, device)."""
+    _check_image(img)
+    device = torch.device(device) if device is not None else None
+    if device is None or device.type != "cuda":
+        raise HipExtError(f"{who}: target device {device} is not a HIP device (the HIP path has no CPU fallback)")
+    if isinstance(img, np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(img)).to(device), device
+    if img.device != device:
+        raise HipExtError(f"{who}: image on {img.device}, expected it on the HIP device {device}")
+    c = img.shape[2]
+    packed = img.stride(2) == 1 and img.stride(1) == c and img.stride(0) >= img.shape[1] * c
+    return (img if packed else img.contiguous()), device
+
+
 def image_to_tensor(img, input_size: int = 518, device=None):
     """``img``: uint8 BGR [h, w, 3] or BGRA [h, w, 4] (alpha ignored) -- a numpy array (copied to ``device``; a non-contiguous one is made
     contiguous first) or a torch tensor on ``device`` (read in place, rows at their own stride: a crop of a decoded frame costs no copy).
     Returns (fp32 [1, 3, H, W] ImageNet-normalised RGB on ``device``, (h, w)), H x W = network_size(h, w, input_size): the reference's
     image2tensor (RAW/dpt.py:196-221)."""
-    _check_image(img)
-    device = torch.device(device) if device is not None else None
-    if device is None or device.type != "cuda":
-        raise HipExtError(f"image_to_tensor: target device {device} is not a HIP device (the HIP path has no CPU fallback)")
-    if isinstance(img, np.ndarray):
-        src = torch.from_numpy(np.ascontiguousarray(img)).to(device)
-    else:
-        if img.device != device:
-            raise HipExtError(f"image_to_tensor: image on {img.device}, expected it on the HIP device {device}")
-        c = img.shape[2]
-        packed = img.stride(2) == 1 and img.stride(1) == c and img.stride(0) >= img.shape[1] * c
-        src = img if packed else img.contiguous()
+    src, device = _stage_image(img, device, "image_to_tensor")
     h, w, c = src.shape
     H, W = network_size(h, w, input_size)
     out = torch.empty(1, 3, H, W, dtype=torch.float32, device=device)
     with torch.cuda.device(device):
         image_prep(src, 1, h, w, c, src.stride(0), h * src.stride(0), H, W, PIXEL_MEAN, PIXEL_STD, out)
     return out, (h, w)
+
+
+def _as_int(v):
+    """Any integer type (int, a numpy integer, a 0-d integer tensor) as a Python int; None for anything else, bool included."""
+    if isinstance(v, bool):
+        return None
+    try:
+        return operator.index(v)
+    except TypeError:
+        return None
+
+
+def _check_size(size, who) -> int:
+    s = _as_int(size)
+    if s is None or s < 14 or s % 14:
+        raise ValueError(f"{who}: size must be a positive multiple of 14 (the patch size), got {size!r}")
+    return s
+
+
+def photo_to_inputs(img, size: int = 518, device=None):
+    """The two network inputs of the amodal pipeline from one decoded photo (reference infer.py:17-18, 83-85).  ``img`` as for image_to_tensor
+    (same checks, same staging, same errors).  Returns (rgb_raw, rgb, (h, w)), both fp32 [1, 3, size, size] in [0, 1] on ``device``:
+    rgb_raw = cv2.resize(img, (size, size)) / 255 (8-bit INTER_LINEAR) for the base-depth network, rgb = Resize(NEAREST)(img / 255) for the
+    amodal one.  The channel order of the photo is KEPT (B, G, R planes for a cv2.imread photo), as the reference keeps it on this path."""
+    size = _check_size(size, "photo_to_inputs")
+    src, device = _stage_image(img, device, "photo_to_inputs")
+    h, w, c = src.shape
+    rgb_raw = torch.empty(1, 3, size, size, dtype=torch.float32, device=device)
+    rgb = torch.empty(1, 3, size, size, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        photo_prep(src, h, w, c, src.stride(0), size, size, raw_out=rgb_raw, near_out=rgb)
+    return rgb_raw, rgb, (h, w)
+
+
+def masks_to_tensor(masks, size: int, device, guide: bool = False):
+    """``masks``: uint8 or bool [h, w] or [K, h, w] (numpy array, copied; or a torch tensor on ``device``, read in place when its rows are
+    packed); any non-zero value is inside.  Returns mask01 fp32 0/1 [K, 1, size, size] on ``device``: F.interpolate(mode="nearest") > 0, the
+    mask of reference infer.py:86-87.  guide=True: (mask01, 2 * mask01 - 1), the second being the network's guide_mask (infer.py:91)."""
+    if isinstance(masks, np.ndarray):
+        dtype_ok = masks.dtype in (np.uint8, np.bool_)
+    elif isinstance(masks, torch.Tensor):
+        dtype_ok = masks.dtype in (torch.uint8, torch.bool)
+    else:
+        raise TypeError(f"masks: expected a numpy array or a torch tensor, got {type(masks).__name__}")
+    if not dtype_ok:
+        raise TypeError(f"masks: expected uint8 or bool, got {masks.dtype}")
+    if masks.ndim not in (2, 3) or min(masks.shape) < 1:
+        raise ValueError(f"masks: expected [h, w] or [K, h, w], got shape {tuple(masks.shape)}")
+    size = _check_size(size, "masks_to_tensor")
+    device = torch.device(device) if device is not None else None
+    if device is None or device.type != "cuda":
+        raise HipExtError(f"masks_to_tensor: target device {device} is not a HIP device (the HIP path has no CPU fallback)")
+    if isinstance(masks, np.ndarray):
+        src = torch.from_numpy(np.ascontiguousarray(masks).view(np.uint8)).to(device)
+    else:
+        if masks.device != device:
+            raise HipExtError(f"masks_to_tensor: masks on {masks.device}, expected them on the HIP device {device}")
+        src = masks
+    if src.dim() == 2:
+        src = src[None]
+    K, h, w = src.shape
+    if not (src.stride(2) == 1 and src.stride(1) >= w and (K == 1 or src.stride(0) >= (h - 1) * src.stride(1) + w)):
+        src = src.contiguous()
+    if src.dtype == torch.bool:
+        src = src.view(torch.uint8)     # one byte per element, 0 / 1: same strides
+    mask01 = torch.empty(K, 1, size, size, dtype=torch.float32, device=device)
+    pm1 = torch.empty_like(mask01) if guide else None
+    with torch.cuda.device(device):
+        mask_prep(src, K, h, w, src.stride(1), src.stride(0), size, size, mask01, pm1)
+    return (mask01, pm1) if guide else mask01
 
 
 def resize_depth(depth: torch.Tensor, h: int, w: int) -> torch.Tensor:
@@ -83,4 +164,20 @@ def resize_depth(depth: torch.Tensor, h: int, w: int) -> torch.Tensor:
     out = torch.empty(depth.shape[0], h, w, dtype=torch.float32, device=depth.device)
     with torch.cuda.device(depth.device):
         depth_resize(depth, out)
+    return out
+
+
+def resize_nearest(depth: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    """fp32 [B, H, W] on the device -> fp32 [B, h, w] with cv2.resize(INTER_NEAREST)'s rule, the resize the reference returns its rendering to the
+    photo's size with (infer.py:77, 113)."""
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3 or depth.dtype != torch.float32:
+        raise HipExtError(f"resize_nearest: expected fp32 [B, H, W], got {getattr(depth, 'dtype', type(depth).__name__)} {tuple(getattr(depth, 'shape', ()))}")
+    hw = _as_int(h), _as_int(w)
+    if None in hw or min(hw) < 1:
+        raise ValueError(f"resize_nearest: the target size must be two positive integers, got {h!r} x {w!r}")
+    h, w = hw
+    depth = depth.contiguous()
+    out = torch.empty(depth.shape[0], h, w, dtype=torch.float32, device=depth.device)
+    with torch.cuda.device(depth.device):
+        nearest_resize(depth, out)
     return out

@@ -7,12 +7,19 @@
 
 The reference moves `base` to the host, normalises it in numpy, sends it back, and blends on the host again; here the
 maps never leave HBM and the only host traffic is the final result.
+
+amodal_infer_image is the whole call, photo and masks in: the preparation of infer.py:17-18, 83-91 on the device (hip_ext.image), the base
+network ONCE per photo, the amodal network as one batch over the K masks, optionally the demo's least-squares alignment over each
+object's visible part (reference app.py:214-216, 249-265), the blend, and optionally the nearest resize back to the photo's size.
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import torch
 
-from . import HipExtError, blend, minmax, normalize
+from . import (EVAL_N, EVAL_SUM_G, EVAL_SUM_P, EVAL_SUM_PG, EVAL_SUM_PP, HipExtError, blend, blend_ex, depth_eval, minmax,
+               normalize)
 
 
 @torch.no_grad()
@@ -36,3 +43,74 @@ def amodal_depth_pipeline(model_raw, amodal_model, rgb: torch.Tensor, mask01: to
     out = torch.empty_like(base_norm)
     blend(pred, base_norm, mask01.reshape(B, H, W).contiguous(), out)
     return base_norm, pred, out
+
+
+AmodalResult = namedtuple("AmodalResult", "base amodal blended masks scale_shift")
+AmodalResult.__doc__ = """fp32 device tensors of amodal_infer_image: base [S, S] (min-max normalised base depth), amodal [K, S, S] (the network's
+prediction, before any alignment), blended [K, S, S], masks [K, S, S] (0 / 1 at the network size), scale_shift [K, 2] or None.  With out_size,
+base and blended are [h, w] / [K, h, w]."""
+
+
+def fit_scale_shift(amodal: torch.Tensor, base: torch.Tensor, visible: torch.Tensor) -> torch.Tensor:
+    """Least-squares (scale, shift) per image with amodal * scale + shift ~ base over visible > 0 (reference app.py:249-261,
+    linear_regression_predict): fp32 [K, 2] on the device, no host read.  From the fp64 sums of ada_depth_eval_fwd:
+    scale = (S_PG - S_P S_G / N) / (S_PP - S_P^2 / N), shift = (S_G - scale S_P) / N.  An image with no visible pixel or a zero
+    denominator gets NaN (N = 0: 0 / 0; denominator 0: masked explicitly, the reference raises there)."""
+    if amodal.shape != base.shape or amodal.shape != visible.shape or amodal.dim() != 3:
+        raise HipExtError(f"fit_scale_shift: [K, H, W] tensors of one shape required, got {tuple(amodal.shape)} {tuple(base.shape)} {tuple(visible.shape)}")
+    vis = (visible > 0).contiguous()
+    s = depth_eval(amodal.contiguous(), base.contiguous(), mask=vis)
+    n, sp, sg, spp, spg = s[:, EVAL_N], s[:, EVAL_SUM_P], s[:, EVAL_SUM_G], s[:, EVAL_SUM_PP], s[:, EVAL_SUM_PG]
+    den = spp - sp * sp / n
+    scale = (spg - sp * sg / n) / den
+    scale = torch.where(den == 0, torch.full_like(scale, float("nan")), scale)
+    shift = (sg - scale * sp) / n
+    return torch.stack([scale, shift], dim=1).float().contiguous()
+
+
+@torch.no_grad()
+def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None, size: int = 518, out_size=None, check: bool = True):
+    """The reference's infer.py call on the device: a decoded uint8 BGR(A) photo [h, w, 3 | 4] and K amodal masks (uint8 / bool [h, w] or
+    [K, h, w]) in, an AmodalResult out.  The base network runs once (B = 1), the amodal network once as a batch of K.
+
+    visible_masks (same layout as masks, K entries): fit the amodal prediction to the base depth over each object's visible part before the
+    paste (fit_scale_shift; the reference's demo, app.py:214-216).  check=True reads scale_shift back once, at the very end, and raises
+    ValueError("Denominator in slope calculation is zero.") for an empty visible mask or a zero / non-finite denominator (app.py:257-258);
+    check=False leaves NaN in scale_shift (and in that image's paste) instead.
+    out_size: None (size x size), (h, w) or "image" (the photo's size): base and blended go through cv2's INTER_NEAREST rule (infer.py:77, 113).
+    An all-zero amodal mask is legal: its blended map equals base."""
+    from .image import _as_int, _check_size, masks_to_tensor, photo_to_inputs, resize_nearest
+    size = _check_size(size, "amodal_infer_image")
+    if not (out_size is None or (isinstance(out_size, str) and out_size == "image")
+            or (isinstance(out_size, (tuple, list)) and len(out_size) == 2 and all((_as_int(v) or 0) > 0 for v in out_size))):
+        raise ValueError(f"amodal_infer_image: out_size must be None, 'image' or (h, w), got {out_size!r}")
+    device = next(amodal_model.parameters()).device
+    rgb_raw, rgb, (h, w) = photo_to_inputs(image, size, device)
+    mask01, guide = masks_to_tensor(masks, size, device, guide=True)
+    K, S = mask01.shape[0], size
+    visible = None
+    if visible_masks is not None:
+        visible = masks_to_tensor(visible_masks, size, device)
+        if visible.shape[0] != K:
+            raise ValueError(f"amodal_infer_image: {visible.shape[0]} visible masks for {K} amodal masks")
+    with torch.cuda.device(device):
+        # the caller-side ImageNet normalisation of infer.py:19 runs inside the raw model's patchify kernel, as in amodal_depth_pipeline
+        base = model_raw(rgb_raw, normalise_input=True).contiguous()              # [1, S, S]: once per photo, whatever K
+        mm = torch.empty(1, 2, dtype=torch.float32, device=device)
+        minmax(base, mm)
+        base_norm = torch.empty_like(base)
+        obs = torch.empty(1, 1, S, S, dtype=torch.float32, device=device)
+        normalize(base, mm, norm=base_norm, obs=obs)
+        pred = amodal_model(rgb.expand(K, -1, -1, -1), guide_rgb=None, guide_mask=guide, observation=obs.expand(K, -1, -1, -1)).reshape(K, S, S).contiguous()
+        base_k = base_norm.expand(K, -1, -1).contiguous()
+        m = mask01.reshape(K, S, S)
+        scale_shift = fit_scale_shift(pred, base_k, visible.reshape(K, S, S)) if visible is not None else None
+        blended = torch.empty_like(pred)
+        blend_ex(pred, base_k, m, blended, scale_shift)
+        base_out = base_norm
+        if out_size is not None:
+            oh, ow = (h, w) if out_size == "image" else out_size
+            base_out, blended = resize_nearest(base_norm, oh, ow), resize_nearest(blended, oh, ow)
+    if check and scale_shift is not None and not bool(torch.isfinite(scale_shift.cpu()).all()):
+        raise ValueError("Denominator in slope calculation is zero.")
+    return AmodalResult(base_out[0], pred, blended, m, scale_shift)

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ADA_ABI_VERSION 9   /* 9: + ada_image_prep_fwd, ada_depth_resize_fwd (the raw model's infer_image; exports only, no signature changed).  History: 8 (round 6): the default-off experiment paths that lost are gone -- ada_igemm_args without ln_stats / ln_colsum / rowstat_out (EP_LNFOLD / EP_ROWSTATS) and the LayerNorm tail (ln_*), no ada_rowstats_finalize.  History: 6 (round 5): + ada_depth_stats_fwd, ada_token_diversity_fwd; 7: ada_igemm_args grows f8_from / f8_mid / f8_scales at its end and split_seg < 0 names the fp8 form of a split output (a zero-filled tail = off: every ABI-6 call means what it meant) */
+#define ADA_ABI_VERSION 10   /* 10: + ada_photo_prep_fwd, ada_mask_prep_fwd, ada_nearest_resize_fwd, ada_blend_ex (the amodal infer_image; exports only, no signature changed).  History: 9: + ada_image_prep_fwd, ada_depth_resize_fwd (the raw model's infer_image; exports only, no signature changed).  History: 8 (round 6): the default-off experiment paths that lost are gone -- ada_igemm_args without ln_stats / ln_colsum / rowstat_out (EP_LNFOLD / EP_ROWSTATS) and the LayerNorm tail (ln_*), no ada_rowstats_finalize.  History: 6 (round 5): + ada_depth_stats_fwd, ada_token_diversity_fwd; 7: ada_igemm_args grows f8_from / f8_mid / f8_scales at its end and split_seg < 0 names the fp8 form of a split output (a zero-filled tail = off: every ABI-6 call means what it meant) */
 
 /* status codes */
 #define ADA_OK 0
@@ -351,6 +351,14 @@ int ada_normalize_fwd(const float* in, const float* minmax, int32_t batch, int64
 int ada_blend_fwd(const float* amodal, const float* base, const float* mask, int32_t batch, int32_t height,
                   int32_t width, float* out, void* stream);
 
+/* ada_blend_fwd with the alignment step of the reference's demo (app.py:214-216, 249-265: linear_regression_predict before median_filter_blend):
+ *   scale_shift  DEVICE fp32 [B, 2] = (scale, shift) per image, or NULL.  The pasted value is amodal * scale + shift in fp32, the product rounded
+ *                before the sum (torch's `slope * x + intercept`, app.py:263: no FMA); base, the paste rule and the border blur are ada_blend_fwd's.
+ *                A NaN pair (an image whose fit had no support) gives NaN inside its mask and on the blurred border.
+ *   NULL         launches the kernel of ada_blend_fwd itself: bit-identical to it. */
+int ada_blend_ex(const float* amodal, const float* base, const float* mask, const float* scale_shift, int32_t batch, int32_t height,
+                 int32_t width, float* out, void* stream);
+
 /* Per-image moments of a sigmoid-head depth map (output of nn.Sigmoid(), reference DA2/dpt.py:146-151): sums[(b * chunks + c) * 2 + {0, 1}] =
  * (sum s, sum s (1 - s)) over chunk c of image b; the caller adds the chunk sums (fixed order, no atomics: bit-reproducible).  sum s(1-s) / sum s
  * is the factor by which the sigmoid compresses the head's logit error in mean|a - b| / mean|b| for this image: hip_ext/engine.py's precision
@@ -386,6 +394,35 @@ int ada_token_diversity_fwd(const void* tap, int64_t ld, int32_t batch, int32_t 
 int ada_image_prep_fwd(const uint8_t* src, int32_t batch, int32_t hi, int32_t wi, int32_t channels, int64_t row_pitch_bytes,
                        int64_t image_stride_bytes, int32_t ho, int32_t wo, const float* mean, const float* std, float* out, void* stream);
 int ada_depth_resize_fwd(const float* in, int32_t batch, int32_t hi, int32_t wi, int32_t ho, int32_t wo, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Host preparation and read-out of the two-model infer.py, which the reference does with OpenCV, torchvision and numpy (infer.py:17-18, 77, 83-91,
+ * 113).  One thread per output pixel, a wave on 64 consecutive x of one output row; ho <= 262140, batch <= 65535.
+ *   ada_photo_prep_fwd      one uint8 HWC photo -> the two network inputs, both fp32 [3, ho, wo], in ONE pass over the output grid; either may be NULL.
+ *     src      uint8 [hi][wi][channels], BGR (3) or BGRA (4: alpha ignored); rows row_pitch_bytes apart (>= wi * channels), as ada_image_prep_fwd.
+ *     CHANNEL ORDER: plane c of both outputs is byte c of a source pixel -- B, G, R for a cv2.imread photo.  The reference never converts BGR to RGB on
+ *     this path (infer.py:17-18, 83) and feeds B, G, R planes to both networks (the raw model's own infer_image does convert: ada_image_prep_fwd).
+ *     raw_out  cv2.resize(img, (wo, ho)) -- INTER_LINEAR on 8-bit pixels -- / 255                                              (infer.py:17-18)
+ *              OpenCV's generic 8-bit path (imgproc/src/resize.cpp, HResizeLinear / VResizeLinear<uchar, int, short>), per axis:
+ *                scale = 1.0 / ((double)n_out / n_in);  f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= s;
+ *                s < 0: s = 0, f = 0;  s >= n_in - 1: s = n_in - 1, f = 0;  second tap min(s + 1, n_in - 1);
+ *                short coefficients a0 = rint((1.f - f) * 2048.f), a1 = rint(f * 2048.f) (fp32 products, half to even)
+ *              horizontal, int32:  h = S[x0] * a0 + S[x1] * a1  on the source rows y0, y1
+ *              vertical:           out = ((((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2)     (255 * 2048 >> 4 = 32640, 32640 * 2048 < 2^31)
+ *              Exception, as in OpenCV: wi == 2 wo AND hi == 2 ho is the 2 x 2 area mean (a + b + c + d + 2) >> 2.
+ *              The quotient is the correctly rounded fp32 v / 255.f.
+ *     near_out torchvision Resize(NEAREST) of photo / 255 (infer.py:83-85) = ATen's nearest rule: scale = (float)n_in / n_out in fp32,
+ *              src = min((int)floorf(dst * scale), n_in - 1).
+ *   ada_mask_prep_fwd       uint8 masks [K][hi][wi] (rows row_pitch_bytes, masks image_stride_bytes apart; any non-zero value is inside) resized with
+ *              the same ATen nearest rule -> out01 fp32 0 / 1 [K, 1, ho, wo] and, optionally, out_pm1 = 2 m - 1, the guide_mask of infer.py:86-91.
+ *   ada_nearest_resize_fwd  fp32 [B, hi, wi] -> [B, ho, wo] with cv2.resize(INTER_NEAREST)'s rule (infer.py:77, 113):
+ *              sx = min((int)floor(dx * ifx), wi - 1), ifx = 1.0 / ((double)wo / wi) in double; the same for y.
+ * ---------------------------------------------------------------------------------------- */
+int ada_photo_prep_fwd(const uint8_t* src, int32_t hi, int32_t wi, int32_t channels, int64_t row_pitch_bytes, int32_t ho, int32_t wo,
+                       float* raw_out, float* near_out, void* stream);
+int ada_mask_prep_fwd(const uint8_t* src, int32_t batch, int32_t hi, int32_t wi, int64_t row_pitch_bytes, int64_t image_stride_bytes,
+                      int32_t ho, int32_t wo, float* out01, float* out_pm1, void* stream);
+int ada_nearest_resize_fwd(const float* in, int32_t batch, int32_t hi, int32_t wi, int32_t ho, int32_t wo, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Tiled inference for inputs larger than the network's native 518 x 518 (the reference squashes every

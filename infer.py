@@ -9,6 +9,10 @@
     blend       : paste amodal depth inside the mask, 3x3 box-blur on the mask border             (infer.py:30-44)
     outputs     : {name}_raw_depth_rendered.png, {name}_amodal_depth_rendered.png                 (infer.py:118-119)
 
+Two opt-in flags go beyond the reference's CLI: --device_prep prepares the photo and the mask on the device too (hip_ext.pipeline.amodal_infer_image:
+cv2's 8-bit INTER_LINEAR restated from OpenCV's arithmetic instead of the float stand-in below, which can move the base network's input by one grey
+level), and --visible_mask_path adds the alignment step of the reference's demo (app.py:214-216, 249-265).  Without them nothing changes.
+
 Differences forced by the environment: the reference hard-codes .cuda() and downloads weights from
 the HF hub; here --device selects the device, --amodal_weights / --raw_weights load local checkpoints, and without
 them deterministic synthetic weights are used (with a warning) so the CLI is runnable offline.
@@ -109,19 +113,39 @@ def _on_device_pipeline(image_bgr, amodal_mask, model_raw, depth_amodal_model, d
     return base_norm[0].cpu(), blended[0].cpu()
 
 
-def infer_single_image(input_image_path, input_mask_path, output_path, model_raw, depth_amodal_model, device="cuda"):
+def _read_mask(path):
+    mask = np.asarray(Image.open(path)) > 0
+    return mask.any(-1) if mask.ndim == 3 else mask
+
+
+def _device_prep_pipeline(image_bgr, amodal_mask, visible_mask, model_raw, depth_amodal_model):
+    """--device_prep: the photo and the masks go to the device as bytes; resizes, both networks, the optional alignment and the blend run there
+    (hip_ext.pipeline.amodal_infer_image).  Returns (base depth, blended depth, mask at the network size as 0 / 255), on the host."""
+    from hip_ext.pipeline import amodal_infer_image
+    res = amodal_infer_image(model_raw, depth_amodal_model, image_bgr, amodal_mask, visible_masks=visible_mask, size=518)
+    return res.base.cpu(), res.blended[0].cpu(), (res.masks[0].cpu().numpy() > 0).astype(np.uint8) * 255
+
+
+def infer_single_image(input_image_path, input_mask_path, output_path, model_raw, depth_amodal_model, device="cuda", device_prep=False,
+                       visible_mask_path=None):
     file_name = os.path.basename(input_image_path).split(".")[0]
     os.makedirs(output_path, exist_ok=True)
     image_bgr = imread_bgr(input_image_path)
     h0, w0 = image_bgr.shape[:2]
+    if visible_mask_path is not None and not device_prep:
+        raise ValueError("--visible_mask_path needs --device_prep (the alignment is part of the on-device call)")
+    if device_prep and not str(device).startswith("cuda"):
+        raise ValueError("--device_prep needs a HIP device")
     if str(device).startswith("cuda"):
-        amodal_mask = np.asarray(Image.open(input_mask_path)) > 0
-        if amodal_mask.ndim == 3:
-            amodal_mask = amodal_mask.any(-1)
-        base_depth, depth_agg = _on_device_pipeline(image_bgr, amodal_mask, model_raw, depth_amodal_model, device)
+        amodal_mask = _read_mask(input_mask_path)
+        if device_prep:
+            visible = _read_mask(visible_mask_path) if visible_mask_path is not None else None
+            base_depth, depth_agg, mask518 = _device_prep_pipeline(image_bgr, amodal_mask, visible, model_raw, depth_amodal_model)
+        else:
+            base_depth, depth_agg = _on_device_pipeline(image_bgr, amodal_mask, model_raw, depth_amodal_model, device)
+            mask518 = (F.interpolate(torch.tensor(amodal_mask).float()[None, None], (518, 518)).squeeze().numpy() > 0).astype(np.uint8) * 255
         raw_colored = (colorize_depth_maps(base_depth.numpy(), 0, 1, cmap="Spectral_r").squeeze() * 255).astype(np.uint8)
         raw_colored_hwc = resize_nearest(chw2hwc(raw_colored), w0, h0)
-        mask518 = (F.interpolate(torch.tensor(amodal_mask).float()[None, None], (518, 518)).squeeze().numpy() > 0).astype(np.uint8) * 255
         agg_colored = (colorize_depth_maps(depth_agg.numpy(), 0, 1, cmap="Spectral_r").squeeze() * 255).astype(np.uint8)
         agg_colored_hwc = resize_nearest(highlight_target(chw2hwc(agg_colored), mask518), w0, h0)
         raw_out, agg_out = raw_colored_hwc[:, :, [2, 1, 0]], agg_colored_hwc[:, :, [2, 1, 0]]
@@ -168,6 +192,12 @@ if __name__ == "__main__":
     parser.add_argument("--amodal_weights", type=str, default=None, help="local directory with config.json + model.safetensors")
     parser.add_argument("--raw_encoder", type=str, default="vitg")
     parser.add_argument("--amodal_encoder", type=str, default="vitl")
+    parser.add_argument("--device_prep", action="store_true", help="resize the photo and the mask on the device as well (cv2's 8-bit arithmetic)")
+    parser.add_argument("--visible_mask_path", type=str, default=None,
+                        help="mask of the object's visible part: fit the amodal depth to the base depth over it before blending (needs --device_prep)")
     args = parser.parse_args()
+    if args.visible_mask_path is not None and not args.device_prep:
+        parser.error("--visible_mask_path needs --device_prep")
     m_raw, m_amodal = load_models(args.device, args.raw_weights, args.amodal_weights, args.raw_encoder, args.amodal_encoder)
-    infer_single_image(args.input_image_path, args.input_mask_path, args.output_folder, m_raw, m_amodal, args.device)
+    infer_single_image(args.input_image_path, args.input_mask_path, args.output_folder, m_raw, m_amodal, args.device,
+                       device_prep=args.device_prep, visible_mask_path=args.visible_mask_path)
