@@ -5,6 +5,8 @@
 // The second half of the file is the host preparation of the two-model infer.py on the device (reference infer.py:17-18, 77, 83-91, 113): the
 // photo resized twice (cv2's 8-bit INTER_LINEAR for the base network, ATen's nearest for the amodal one) in one pass, the amodal masks, and the
 // cv2 INTER_NEAREST resize of a result back to the photo.  Same launch shape, same rule: one thread per output pixel, no scratch.
+// The last kernel is the rendering of infer.py:106-119 (colour map, highlight_target, the nearest resize to the photo's size, the channel flip) in one
+// pass over the output grid: uint8 pixels out, optionally the 16-bit map beside them.
 #include "ada_common.h"
 
 namespace {
@@ -211,17 +213,151 @@ struct NearestArgs {
     double ify, ifx;         // 1 / ((double)ho / hi), 1 / ((double)wo / wi)
 };
 
-// cv2.resize(INTER_NEAREST) (resizeNN): sx = min((int)floor(dx * ifx), wi - 1) in double, the same for y.  Block (64, 4), grid z = image.
+// cv2.resize(INTER_NEAREST)'s source index (resizeNN): min((int)floor(d * inv), n_in - 1) in double, inv = 1 / ((double)n_out / n_in)
+ADA_DEV int cv2_nearest_src(int d, double inv, int n_in) {
+    const int s = (int)__builtin_floor((double)d * inv);
+    return s < n_in - 1 ? s : n_in - 1;
+}
+
+// cv2.resize(INTER_NEAREST): cv2_nearest_src on both axes.  Block (64, 4), grid z = image.
 __global__ __launch_bounds__(256) void nearest_resize_kernel(NearestArgs a) {
     const int dx = blockIdx.x * 64 + threadIdx.x;
     const int dy = blockIdx.y * 4 + threadIdx.y;
     const int b = blockIdx.z;
     if (dx >= a.wo || dy >= a.ho) return;
-    int sx = (int)__builtin_floor((double)dx * a.ifx);
-    int sy = (int)__builtin_floor((double)dy * a.ify);
-    sx = sx < a.wi - 1 ? sx : a.wi - 1;
-    sy = sy < a.hi - 1 ? sy : a.hi - 1;
+    const int sx = cv2_nearest_src(dx, a.ifx, a.wi);
+    const int sy = cv2_nearest_src(dy, a.ify, a.hi);
     a.out[((long)b * a.ho + dy) * a.wo + dx] = a.in[((long)b * a.hi + sy) * a.wi + sx];
+}
+
+struct RenderArgs {
+    const float* depth;      // [B, hi, wi]
+    const float* minmax;     // [B, 2] or NULL
+    const uint8_t* lut;      // [256][3], R, G, B
+    const float* mask;       // [B, hi, wi] or NULL
+    uint8_t* out;            // [B, ho, wo, 3] or NULL
+    uint16_t* out_u16;       // [B, ho, wo] or NULL
+    int hi, wi, ho, wo;
+    double ify, ifx;         // 1 / ((double)ho / hi), 1 / ((double)wo / wi)
+    float lo, span;          // used when minmax == NULL
+    double keep, fg;         // 1.0 - alpha, alpha * 200.0
+    int overlay;             // mask != NULL && alpha != 0
+    int radius;              // thickness - 1
+    uint32_t outline;        // packed as a pixel below
+    int bgr;
+};
+
+// a pixel in a register: R | G << 8 | B << 16, the order of the bytes in memory
+ADA_DEV uint32_t pack_rgb(uint32_t r, uint32_t g, uint32_t b) { return r | (g << 8) | (b << 16); }
+
+// highlight_target's overlay of one byte (infer.py:50): (uint8)((1 - alpha) * c + alpha * 200) in double, both products rounded before the sum
+ADA_DEV uint32_t overlay_byte(uint32_t c, double keep, double fg) {
+#pragma clang fp contract(off)
+    return (uint32_t)(keep * (double)c + fg);
+}
+
+ADA_DEV bool inside(float m) { return m > 0.f; }
+
+// draw_mask_outline's edge: an inside pixel with a 4-neighbour outside; neighbours past the image take the border pixel's value
+ADA_DEV bool mask_edge(const float* m, int v, int u, int hi, int wi) {
+    const float* row = m + (long)v * wi;
+    if (!inside(row[u])) return false;
+    const float* up = m + (long)(v > 0 ? v - 1 : 0) * wi;
+    const float* dn = m + (long)(v < hi - 1 ? v + 1 : hi - 1) * wi;
+    return !(inside(up[u]) && inside(dn[u]) && inside(row[u > 0 ? u - 1 : 0]) && inside(row[u < wi - 1 ? u + 1 : wi - 1]));
+}
+
+// ... dilated thickness - 1 times with a zero-padded cross: some in-image edge pixel within L1 distance `radius`
+ADA_DEV bool near_edge(const float* m, int sy, int sx, int hi, int wi, int radius) {
+    for (int dv = -radius; dv <= radius; ++dv) {
+        const int v = sy + dv;
+        if (v < 0 || v >= hi) continue;
+        const int w = radius - (dv < 0 ? -dv : dv);
+        const int u0 = sx - w > 0 ? sx - w : 0, u1 = sx + w < wi - 1 ? sx + w : wi - 1;
+        for (int u = u0; u <= u1; ++u)
+            if (mask_edge(m, v, u, hi, wi)) return true;
+    }
+    return false;
+}
+
+// Block (64, 4), grid z = image; a thread renders PPT consecutive pixels of one output row.  PPT = 1 stores three bytes (and one u16) per thread and
+// takes any width and any pointer; PPT = 4 stores the twelve bytes of its four pixels as three dwords (and the four u16 as two), which needs
+// wo % 4 == 0 and aligned pointers (the launcher picks).  Everything but the store is a function of the SOURCE pixel -- nearest resize is a pure
+// gather, so rendering what was gathered is the reference's render-then-resize -- and neighbouring outputs of an up-sampling share it: a pixel
+// whose source column is its left neighbour's reuses that result.  The colour table sits in LDS twice, plain and with the overlay applied
+// (the overlay acts on table colours only: the outline is painted over it), so the double arithmetic is done 768 times per block, not per pixel.
+template <int PPT>
+__global__ __launch_bounds__(256) void depth_render_kernel(RenderArgs a) {
+    __shared__ uint32_t lut[2][256];
+    {
+        const int i = threadIdx.y * 64 + threadIdx.x;
+        const uint32_t r = a.lut[3 * i], g = a.lut[3 * i + 1], b = a.lut[3 * i + 2];
+        lut[0][i] = pack_rgb(r, g, b);
+        lut[1][i] = a.overlay ? pack_rgb(overlay_byte(r, a.keep, a.fg), overlay_byte(g, a.keep, a.fg), overlay_byte(b, a.keep, a.fg)) : pack_rgb(r, g, b);
+    }
+    __syncthreads();
+    const int dx0 = (blockIdx.x * 64 + threadIdx.x) * PPT;
+    const int dy = blockIdx.y * 4 + threadIdx.y;
+    const int b = blockIdx.z;
+    if (dx0 >= a.wo || dy >= a.ho) return;
+    float lo = a.lo, span = a.span;
+    if (a.minmax) {
+        lo = a.minmax[2 * b];
+        span = a.minmax[2 * b + 1] - lo;
+    }
+    const uint32_t nan_ov = a.overlay ? overlay_byte(0, a.keep, a.fg) * 0x010101u : 0u;   // a NaN pixel is black before the overlay
+    const int sy = cv2_nearest_src(dy, a.ify, a.hi);
+    const float* drow = a.depth + ((long)b * a.hi + sy) * a.wi;
+    const float* mimg = a.mask ? a.mask + (long)b * a.hi * a.wi : nullptr;
+    uint32_t px[PPT], t16[PPT];
+    int prev = -1;
+#pragma unroll
+    for (int j = 0; j < PPT; ++j) {
+        const int sx = cv2_nearest_src(dx0 + j, a.ifx, a.wi);
+        if (j > 0 && sx == prev) {
+            px[j] = px[j - 1];
+            t16[j] = t16[j - 1];
+            continue;
+        }
+        prev = sx;
+        float t = (drow[sx] - lo) / span;          // two roundings, IEEE division: numpy's (d - lo) / span
+        t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);   // np.clip: NaN passes through
+        const bool nan = t != t;
+        int idx = nan ? 0 : (int)(t * 256.f);
+        idx = idx < 255 ? idx : 255;
+        bool ov = false, paint = false;
+        if (mimg) {
+            ov = mimg[(long)sy * a.wi + sx] == 0.f;
+            paint = near_edge(mimg, sy, sx, a.hi, a.wi, a.radius);
+        }
+        uint32_t c = nan ? (ov ? nan_ov : 0u) : lut[ov ? 1 : 0][idx];
+        if (paint) c = a.outline;
+        if (a.bgr) c = (c & 0x00ff00u) | (c >> 16) | ((c & 0xffu) << 16);
+        px[j] = c;
+        t16[j] = nan ? 0u : (uint32_t)(t * 65535.f);
+    }
+    const long o = ((long)b * a.ho + dy) * a.wo + dx0;
+    if (PPT == 1) {
+        if (a.out) {
+            uint8_t* p = a.out + o * 3;
+            p[0] = (uint8_t)px[0];
+            p[1] = (uint8_t)(px[0] >> 8);
+            p[2] = (uint8_t)(px[0] >> 16);
+        }
+        if (a.out_u16) a.out_u16[o] = (uint16_t)t16[0];
+    } else {
+        if (a.out) {
+            uint32_t* p = reinterpret_cast<uint32_t*>(a.out + o * 3);      // o % 4 == 0: 12-byte steps from an aligned base
+            p[0] = px[0] | (px[PPT > 1 ? 1 : 0] << 24);
+            p[1] = (px[PPT > 1 ? 1 : 0] >> 8) | (px[PPT > 2 ? 2 : 0] << 16);
+            p[2] = (px[PPT > 2 ? 2 : 0] >> 16) | (px[PPT > 3 ? 3 : 0] << 8);
+        }
+        if (a.out_u16) {
+            uint32_t* q = reinterpret_cast<uint32_t*>(a.out_u16 + o);
+            q[0] = t16[0] | (t16[PPT > 1 ? 1 : 0] << 16);
+            q[1] = t16[PPT > 2 ? 2 : 0] | (t16[PPT > 3 ? 3 : 0] << 16);
+        }
+    }
 }
 
 }  // namespace
@@ -312,4 +448,35 @@ extern "C" int ada_nearest_resize_fwd(const float* in, int32_t batch, int32_t hi
     hipLaunchKernelGGL(nearest_resize_kernel, dim3((unsigned)((wo + 63) / 64), (unsigned)((ho + 3) / 4), (unsigned)batch), dim3(64, 4), 0,
                        (hipStream_t)stream, a);
     return ada_check_launch("ada_nearest_resize_fwd");
+}
+
+extern "C" int ada_depth_render_fwd(const float* depth, int32_t batch, int32_t hi, int32_t wi, const float* minmax, float lo, float hi_value,
+                                    const uint8_t* lut, const float* mask, int32_t thickness, uint32_t outline_rgb, double alpha,
+                                    int32_t ho, int32_t wo, int32_t bgr, uint8_t* out, uint16_t* out_u16, void* stream) {
+    ADA_REQUIRE(depth && lut, ADA_EINVAL, "ada_depth_render_fwd: null pointer");
+    ADA_REQUIRE(out || out_u16, ADA_EINVAL, "ada_depth_render_fwd: null pointer (both outputs)");
+    ADA_REQUIRE(batch > 0 && hi > 0 && wi > 0 && ho > 0 && wo > 0, ADA_EINVAL, "ada_depth_render_fwd: bad shape batch=%d %dx%d -> %dx%d", batch, hi, wi, ho, wo);
+    ADA_REQUIRE(thickness >= 1 && thickness <= 4, ADA_EINVAL, "ada_depth_render_fwd: thickness %d (1..4)", thickness);
+    ADA_REQUIRE(outline_rgb <= 0xffffffu, ADA_EINVAL, "ada_depth_render_fwd: outline colour 0x%x is not 0xRRGGBB", outline_rgb);
+    ADA_REQUIRE(alpha >= 0.0 && alpha <= 1.0, ADA_EINVAL, "ada_depth_render_fwd: alpha %g outside [0, 1]", alpha);
+    ADA_REQUIRE((ho + 3) / 4 <= 65535 && batch <= 65535, ADA_EUNSUPPORTED, "ada_depth_render_fwd: ho / batch exceed the grid limits");
+    RenderArgs a;
+    a.depth = depth; a.minmax = minmax; a.lut = lut; a.mask = mask; a.out = out; a.out_u16 = out_u16;
+    a.hi = hi; a.wi = wi; a.ho = ho; a.wo = wo;
+    a.ify = 1.0 / ((double)ho / hi);
+    a.ifx = 1.0 / ((double)wo / wi);
+    a.lo = lo;
+    a.span = (float)((double)hi_value - (double)lo);
+    a.keep = 1.0 - alpha;
+    a.fg = alpha * 200.0;
+    a.overlay = (mask && alpha != 0.0) ? 1 : 0;
+    a.radius = thickness - 1;
+    a.outline = ((outline_rgb >> 16) & 0xffu) | (outline_rgb & 0x00ff00u) | ((outline_rgb & 0xffu) << 16);
+    a.bgr = bgr ? 1 : 0;
+    const dim3 block(64, 4);
+    if (wo % 4 == 0 && (uintptr_t)out % 4 == 0 && (uintptr_t)out_u16 % 8 == 0)
+        hipLaunchKernelGGL(depth_render_kernel<4>, dim3((unsigned)((wo + 255) / 256), (unsigned)((ho + 3) / 4), (unsigned)batch), block, 0, (hipStream_t)stream, a);
+    else
+        hipLaunchKernelGGL(depth_render_kernel<1>, dim3((unsigned)((wo + 63) / 64), (unsigned)((ho + 3) / 4), (unsigned)batch), block, 0, (hipStream_t)stream, a);
+    return ada_check_launch("ada_depth_render_fwd");
 }

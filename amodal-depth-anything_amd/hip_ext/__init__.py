@@ -30,7 +30,7 @@ EXPORTS = (
     "ada_pos_embed_resize", "ada_layernorm_fwd", "ada_layernorm_ex", "ada_patchify", "ada_write_cls", "ada_bilinear_fwd", "ada_selftest",
     "ada_minmax_fwd", "ada_depth_stats_fwd", "ada_token_diversity_fwd", "ada_normalize_fwd", "ada_blend_fwd", "ada_depth_eval_fwd", "ada_tile_blend_fwd", "ada_dpt_tail_fwd", "ada_tapsum_resize_fwd",
     "ada_image_prep_fwd", "ada_depth_resize_fwd",
-    "ada_photo_prep_fwd", "ada_mask_prep_fwd", "ada_nearest_resize_fwd", "ada_blend_ex",
+    "ada_photo_prep_fwd", "ada_mask_prep_fwd", "ada_nearest_resize_fwd", "ada_blend_ex", "ada_depth_render_fwd",
     "ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_last_tile",
     "ada_debug_set_timestamps", "ada_debug_set_attention_variant", "ada_debug_count_saturated",
 )
@@ -158,6 +158,9 @@ def load(path: Optional[str] = None):
     lib.ada_nearest_resize_fwd.restype = c_int
     lib.ada_blend_ex.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]
     lib.ada_blend_ex.restype = c_int
+    lib.ada_depth_render_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_int32, ctypes.c_uint32,
+                                         c_double, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.ada_depth_render_fwd.restype = c_int
     for name in ("ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_set_attention_variant"):
         getattr(lib, name).argtypes = [c_int]
         getattr(lib, name).restype = None
@@ -487,6 +490,31 @@ def nearest_resize(inp, out):
     B, hi, wi = inp.shape
     _check(load().ada_nearest_resize_fwd(_dev(inp, "in", torch.float32), B, hi, wi, out.shape[1], out.shape[2], _dev(out, "out", torch.float32), _stream()),
            "ada_nearest_resize_fwd")
+
+
+def depth_render(depth, lut, ho, wo, out=None, out_u16=None, *, minmax=None, vmin=0.0, vmax=1.0, mask=None, thickness=2, outline_rgb=0,
+                 alpha=0.0, bgr=False):
+    """depth fp32 [B, hi, wi] -> out uint8 [B, ho, wo, 3] and / or out_u16 uint16 [B, ho, wo] (ada_depth_render_fwd): (d - lo) / span clipped, the
+    256-entry colour table ``lut`` (uint8 [256, 3], R, G, B), with ``mask`` (fp32 [B, hi, wi]) the overlay and the outline of highlight_target, the
+    cv2 nearest resize to ho x wo, B, G, R bytes with ``bgr``.  lo / span come from ``minmax`` (device fp32 [B, 2]) when given, else from vmin /
+    vmax.  ``outline_rgb`` is 0xRRGGBB.  Every tensor is contiguous and on one device; the output buffers may be larger than the sizes say."""
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3 or not depth.is_contiguous():
+        raise HipExtError(f"depth_render: depth must be a contiguous [B, H, W] tensor, got {tuple(getattr(depth, 'shape', ()))}")
+    B, hi, wi = depth.shape
+    n = B * ho * wo
+    for name, t, need in (("lut", lut, 768), ("mask", mask, depth.numel()), ("minmax", minmax, 2 * B), ("out", out, 3 * n), ("out_u16", out_u16, n)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_contiguous() or t.numel() < need:
+            raise HipExtError(f"depth_render: {name} must be a contiguous tensor of at least {need} elements, got {tuple(getattr(t, 'shape', ()))}")
+        if t.device != depth.device:
+            raise HipExtError(f"depth_render: {name} on {t.device}, depth on {depth.device}")
+    if mask is not None and mask.shape != depth.shape:
+        raise HipExtError(f"depth_render: mask {tuple(mask.shape)} does not match depth {tuple(depth.shape)}")
+    _check(load().ada_depth_render_fwd(_dev(depth, "depth", torch.float32), B, hi, wi, _opt(minmax, "minmax", torch.float32), float(vmin), float(vmax),
+                                       _dev(lut, "lut", torch.uint8), _opt(mask, "mask", torch.float32), int(thickness), int(outline_rgb), float(alpha),
+                                       int(ho), int(wo), int(bool(bgr)), _opt(out, "out", torch.uint8), _opt(out_u16, "out_u16", torch.uint16), _stream()),
+           "ada_depth_render_fwd")
 
 
 # --- tuning / diagnostic hooks (include/ada_hip.h, last section) ---------------------------------

@@ -7,6 +7,10 @@ another resizes the depth map back to the photo (ada_depth_resize_fwd).  Only th
 The two-model pipeline of infer.py prepares its photo differently (reference infer.py:17-18, 83-91): no BGR -> RGB, a square size x size squash,
 cv2's 8-bit INTER_LINEAR for the base network and torchvision's nearest for the amodal one, and nearest-resized masks.  photo_to_inputs,
 masks_to_tensor and resize_nearest do that on the device (ada_photo_prep_fwd, ada_mask_prep_fwd, ada_nearest_resize_fwd).
+
+render_depth is the other end of infer.py (reference infer.py:106-119): colour map, highlight_target, the nearest resize to the photo's size and the
+channel flip in one kernel (ada_depth_render_fwd), uint8 pixels out.  The outline it paints is the tree's stand-in (src/util/image_util.py
+draw_mask_outline), not cv2.findContours / drawContours: there is no cv2 here to pin those against.
 """
 from __future__ import annotations
 
@@ -15,7 +19,7 @@ import operator
 import numpy as np
 import torch
 
-from . import HipExtError, depth_resize, image_prep, mask_prep, nearest_resize, photo_prep
+from . import HipExtError, depth_render, depth_resize, image_prep, mask_prep, nearest_resize, photo_prep
 
 PIXEL_MEAN = (0.485, 0.456, 0.406)
 PIXEL_STD = (0.229, 0.224, 0.225)
@@ -181,3 +185,71 @@ def resize_nearest(depth: torch.Tensor, h: int, w: int) -> torch.Tensor:
     with torch.cuda.device(depth.device):
         nearest_resize(depth, out)
     return out
+
+
+_LUTS = {}
+
+
+def colormap_lut(cmap: str = "Spectral_r", device=None) -> torch.Tensor:
+    """The 256 colours of a matplotlib colour map as uint8 [256, 3] (R, G, B) on ``device``: (cmap(i)[:3] * 255).astype(uint8), the table
+    ada_depth_render_fwd indexes with min((int)(t * 256), 255).  Cached per (name, device).  A map that does not have 256 entries is refused:
+    the index rule assumes them."""
+    import matplotlib
+    cm = matplotlib.colormaps[cmap]
+    if cm.N != 256:
+        raise ValueError(f"colormap_lut: colour map {cmap!r} has {cm.N} entries, the renderer needs 256")
+    device = torch.device(device) if device is not None else torch.device("cpu")
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (cmap, device)
+    if key not in _LUTS:
+        table = (cm(np.arange(256))[:, :3] * 255).astype(np.uint8)
+        _LUTS[key] = torch.from_numpy(np.ascontiguousarray(table)).to(device)
+    return _LUTS[key]
+
+
+def render_depth(depth, masks=None, out_size=None, cmap="Spectral_r", vmin=0.0, vmax=1.0, minmax=None, thickness=2, outline=(0, 0, 0), alpha=0.0,
+                 bgr=True, u16=False):
+    """fp32 depth maps [B, H, W] on the device -> uint8 [B, h, w, 3] on the device, the pictures of reference infer.py:106-119:
+    ((d - vmin) / (vmax - vmin)).clip(0, 1) through the colour map ``cmap``; with ``masks`` (fp32 [B, H, W], > 0 inside) highlight_target's
+    overlay (``alpha``, towards grey 200 outside the mask) and outline (``thickness`` 1..4, ``outline`` = (R, G, B) bytes; the stand-in of
+    src/util/image_util.py, not cv2's contours); cv2.resize(INTER_NEAREST) to ``out_size`` = (h, w) (None: H x W); B, G, R bytes with ``bgr``.
+    ``minmax``: device fp32 [B, 2] (hip_ext.minmax) used per image instead of vmin / vmax.  u16=True: (rendering, uint16 [B, h, w]), the
+    16-bit map of infer.py:107-108.  Nothing is read back to the host."""
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3 or depth.dtype != torch.float32:
+        raise HipExtError(f"render_depth: expected fp32 [B, H, W], got {getattr(depth, 'dtype', type(depth).__name__)} {tuple(getattr(depth, 'shape', ()))}")
+    if not depth.is_cuda:
+        raise HipExtError(f"render_depth: depth on {depth.device}, expected a HIP device (the HIP path has no CPU fallback)")
+    B, H, W = depth.shape
+    if masks is not None and (not isinstance(masks, torch.Tensor) or masks.dtype != torch.float32 or masks.shape != depth.shape or masks.device != depth.device):
+        raise HipExtError(f"render_depth: masks must be fp32 {tuple(depth.shape)} on {depth.device}, got "
+                          f"{getattr(masks, 'dtype', type(masks).__name__)} {tuple(getattr(masks, 'shape', ()))}")
+    if minmax is not None and (not isinstance(minmax, torch.Tensor) or minmax.dtype != torch.float32 or tuple(minmax.shape) != (B, 2)
+                               or minmax.device != depth.device):
+        raise HipExtError(f"render_depth: minmax must be fp32 [{B}, 2] on {depth.device}, got "
+                          f"{getattr(minmax, 'dtype', type(minmax).__name__)} {tuple(getattr(minmax, 'shape', ()))}")
+    if out_size is None:
+        h, w = H, W
+    else:
+        hw = tuple(_as_int(v) for v in out_size) if isinstance(out_size, (tuple, list)) and len(out_size) == 2 else (None, None)
+        if None in hw or min(hw) < 1:
+            raise ValueError(f"render_depth: out_size must be None or two positive integers (h, w), got {out_size!r}")
+        h, w = hw
+    t = _as_int(thickness)
+    if t is None or not 1 <= t <= 4:
+        raise ValueError(f"render_depth: thickness must be 1..4, got {thickness!r}")
+    rgb = tuple(_as_int(v) for v in outline) if isinstance(outline, (tuple, list)) and len(outline) == 3 else (None,)
+    if None in rgb or not all(0 <= v <= 255 for v in rgb):
+        raise ValueError(f"render_depth: outline must be three bytes (R, G, B), got {outline!r}")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"render_depth: alpha must lie in [0, 1], got {alpha!r}")
+    if minmax is None and float(vmax) == float(vmin):
+        raise ValueError(f"render_depth: vmax == vmin ({vmin!r}): nothing to normalise by")
+    lut = colormap_lut(cmap, depth.device)
+    out = torch.empty(B, h, w, 3, dtype=torch.uint8, device=depth.device)
+    out16 = torch.empty(B, h, w, dtype=torch.uint16, device=depth.device) if u16 else None
+    with torch.cuda.device(depth.device):
+        depth_render(depth.contiguous(), lut, h, w, out, out16, minmax=None if minmax is None else minmax.contiguous(), vmin=vmin, vmax=vmax,
+                     mask=None if masks is None else masks.contiguous(), thickness=t, outline_rgb=(rgb[0] << 16) | (rgb[1] << 8) | rgb[2],
+                     alpha=float(alpha), bgr=bgr)
+    return (out, out16) if u16 else out

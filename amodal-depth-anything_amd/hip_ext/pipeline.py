@@ -51,6 +51,12 @@ prediction, before any alignment), blended [K, S, S], masks [K, S, S] (0 / 1 at 
 base and blended are [h, w] / [K, h, w]."""
 
 
+AmodalRendered = namedtuple("AmodalRendered", AmodalResult._fields + ("raw_rendered", "amodal_rendered"))
+AmodalRendered.__doc__ = """amodal_infer_image(render=True): the five fields of AmodalResult, then the pictures of reference infer.py:106-119 as uint8 device tensors
+in B, G, R order at out_size (the network size when out_size is None): raw_rendered [h, w, 3] (the base depth, no mask) and amodal_rendered
+[K, h, w, 3] (the blended depth with highlight_target's outline and overlay)."""
+
+
 def fit_scale_shift(amodal: torch.Tensor, base: torch.Tensor, visible: torch.Tensor) -> torch.Tensor:
     """Least-squares (scale, shift) per image with amodal * scale + shift ~ base over visible > 0 (reference app.py:249-261,
     linear_regression_predict): fp32 [K, 2] on the device, no host read.  From the fp64 sums of ada_depth_eval_fwd:
@@ -69,7 +75,8 @@ def fit_scale_shift(amodal: torch.Tensor, base: torch.Tensor, visible: torch.Ten
 
 
 @torch.no_grad()
-def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None, size: int = 518, out_size=None, check: bool = True):
+def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None, size: int = 518, out_size=None, check: bool = True,
+                       render: bool = False):
     """The reference's infer.py call on the device: a decoded uint8 BGR(A) photo [h, w, 3 | 4] and K amodal masks (uint8 / bool [h, w] or
     [K, h, w]) in, an AmodalResult out.  The base network runs once (B = 1), the amodal network once as a batch of K.
 
@@ -78,8 +85,10 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
     ValueError("Denominator in slope calculation is zero.") for an empty visible mask or a zero / non-finite denominator (app.py:257-258);
     check=False leaves NaN in scale_shift (and in that image's paste) instead.
     out_size: None (size x size), (h, w) or "image" (the photo's size): base and blended go through cv2's INTER_NEAREST rule (infer.py:77, 113).
-    An all-zero amodal mask is legal: its blended map equals base."""
-    from .image import _as_int, _check_size, masks_to_tensor, photo_to_inputs, resize_nearest
+    An all-zero amodal mask is legal: its blended map equals base.
+    render=True: an AmodalRendered -- the same five fields plus the two pictures of infer.py:106-119 (hip_ext.image.render_depth: Spectral_r, the
+    outline and overlay of highlight_target on the amodal ones, B, G, R), rendered from the network-size maps straight to out_size."""
+    from .image import _as_int, _check_size, masks_to_tensor, photo_to_inputs, render_depth, resize_nearest
     size = _check_size(size, "amodal_infer_image")
     if not (out_size is None or (isinstance(out_size, str) and out_size == "image")
             or (isinstance(out_size, (tuple, list)) and len(out_size) == 2 and all((_as_int(v) or 0) > 0 for v in out_size))):
@@ -108,9 +117,14 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
         blended = torch.empty_like(pred)
         blend_ex(pred, base_k, m, blended, scale_shift)
         base_out = base_norm
-        if out_size is not None:
-            oh, ow = (h, w) if out_size == "image" else out_size
-            base_out, blended = resize_nearest(base_norm, oh, ow), resize_nearest(blended, oh, ow)
+        target = None if out_size is None else ((h, w) if out_size == "image" else tuple(out_size))
+        if render:
+            raw_rendered = render_depth(base_norm, out_size=target)
+            amodal_rendered = render_depth(blended, m, out_size=target)
+        if target is not None:
+            base_out, blended = resize_nearest(base_norm, *target), resize_nearest(blended, *target)
     if check and scale_shift is not None and not bool(torch.isfinite(scale_shift.cpu()).all()):
         raise ValueError("Denominator in slope calculation is zero.")
+    if render:
+        return AmodalRendered(base_out[0], pred, blended, m, scale_shift, raw_rendered[0], amodal_rendered)
     return AmodalResult(base_out[0], pred, blended, m, scale_shift)

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ADA_ABI_VERSION 10   /* 10: + ada_photo_prep_fwd, ada_mask_prep_fwd, ada_nearest_resize_fwd, ada_blend_ex (the amodal infer_image; exports only, no signature changed).  History: 9: + ada_image_prep_fwd, ada_depth_resize_fwd (the raw model's infer_image; exports only, no signature changed).  History: 8 (round 6): the default-off experiment paths that lost are gone -- ada_igemm_args without ln_stats / ln_colsum / rowstat_out (EP_LNFOLD / EP_ROWSTATS) and the LayerNorm tail (ln_*), no ada_rowstats_finalize.  History: 6 (round 5): + ada_depth_stats_fwd, ada_token_diversity_fwd; 7: ada_igemm_args grows f8_from / f8_mid / f8_scales at its end and split_seg < 0 names the fp8 form of a split output (a zero-filled tail = off: every ABI-6 call means what it meant) */
+#define ADA_ABI_VERSION 10   /* 10: + ada_photo_prep_fwd, ada_mask_prep_fwd, ada_nearest_resize_fwd, ada_blend_ex (the amodal infer_image; exports only, no signature changed); later, still 10: + ada_depth_render_fwd (the rendering of infer.py:106-119; one more export, no signature changed, so a caller built against the earlier 10 runs unchanged).  History: 9: + ada_image_prep_fwd, ada_depth_resize_fwd (the raw model's infer_image; exports only, no signature changed).  History: 8 (round 6): the default-off experiment paths that lost are gone -- ada_igemm_args without ln_stats / ln_colsum / rowstat_out (EP_LNFOLD / EP_ROWSTATS) and the LayerNorm tail (ln_*), no ada_rowstats_finalize.  History: 6 (round 5): + ada_depth_stats_fwd, ada_token_diversity_fwd; 7: ada_igemm_args grows f8_from / f8_mid / f8_scales at its end and split_seg < 0 names the fp8 form of a split output (a zero-filled tail = off: every ABI-6 call means what it meant) */
 
 /* status codes */
 #define ADA_OK 0
@@ -423,6 +423,37 @@ int ada_photo_prep_fwd(const uint8_t* src, int32_t hi, int32_t wi, int32_t chann
 int ada_mask_prep_fwd(const uint8_t* src, int32_t batch, int32_t hi, int32_t wi, int64_t row_pitch_bytes, int64_t image_stride_bytes,
                       int32_t ho, int32_t wo, float* out01, float* out_pm1, void* stream);
 int ada_nearest_resize_fwd(const float* in, int32_t batch, int32_t hi, int32_t wi, int32_t ho, int32_t wo, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The rendering of infer.py:106-119 in ONE pass over the output grid [batch, ho, wo]: min-max normalisation (infer.py:22 / colorize_depth_maps), the
+ * colour map, highlight_target (infer.py:46-57), cv2.resize(INTER_NEAREST) to the photo's size and the channel flip.  The library allocates nothing.
+ *   depth     fp32 [batch, hi, wi];  mask  fp32 [batch, hi, wi] or NULL (no highlight);  both contiguous
+ *   source    output pixel (dy, dx) shows source pixel (sy, sx) by ada_nearest_resize_fwd's rule (the same device function).  Nearest resize is a
+ *             pure gather, so rendering the gathered pixel equals the reference's render-then-resize.
+ *   normalise t = (d - lo) / span, every operation rounded to fp32 (no FMA, IEEE division), then clipped to [0, 1].
+ *             minmax == NULL:  lo is the argument, span = (float)((double)hi_value - (double)lo)
+ *             minmax != NULL:  DEVICE fp32 [batch, 2] (what ada_minmax_fwd writes): lo = minmax[b][0], span = minmax[b][1] - minmax[b][0] in fp32
+ *             NaN stays NaN (span == 0 on a constant map: 0 / 0), +-inf clips.
+ *   colour    idx = min((int)(t * 256.f), 255), rgb = lut[idx]; a NaN t is (0, 0, 0).  lut: DEVICE uint8 [256][3] in R, G, B order, the caller's.
+ *             With lut[i] = (cmap(i)[:3] * 255).astype(uint8) this is (cmap(clip(x))[..., :3] * 255).astype(uint8) of a 256-entry matplotlib map, byte for byte.
+ *   overlay   mask != NULL and alpha != 0: where the mask is 0 each byte becomes (uint8)((1.0 - alpha) * c + alpha * 200.0), in double, both products
+ *             rounded before the sum, the result truncated.  alpha == 0 leaves the bytes alone.  alpha must lie in [0, 1].
+ *   outline   mask != NULL: the tree's stand-in draw_mask_outline (src/util/image_util.py), bit for bit -- NOT cv2.findContours / drawContours, which
+ *             there is no cv2 here to pin against.  inside = mask > 0;
+ *               edge(v, u) = inside(v, u) && !(inside(v-1, u) && inside(v+1, u) && inside(v, u-1) && inside(v, u+1)), neighbours past the image taking the
+ *               border pixel's value (a mask that fills the image has no edge);
+ *               a pixel is painted outline_rgb (0xRRGGBB) when some in-image (v, u) with |v - sy| + |u - sx| <= thickness - 1 is an edge (the dilation
+ *               is zero-padded).  thickness: 1..4 (the reference draws 2), checked whether or not a mask is given.
+ *   out       uint8 [batch, ho, wo, 3] packed, R, G, B -- or B, G, R when bgr != 0 (infer.py:115-116); overlay and outline colours are R, G, B before the
+ *             flip.  May be NULL.
+ *   out_u16   uint16 [batch, ho, wo] = (uint16_t)(t * 65535.f), truncated, NaN -> 0; mask and outline do not apply (the 16-bit save of infer.py:107-108).
+ *             May be NULL, but not both.
+ * One thread per output pixel, or four with dword stores when wo % 4 == 0 and out / out_u16 are 4- / 8-byte aligned: same bytes either way.
+ * ho <= 262140, batch <= 65535.
+ * ---------------------------------------------------------------------------------------- */
+int ada_depth_render_fwd(const float* depth, int32_t batch, int32_t hi, int32_t wi, const float* minmax, float lo, float hi_value,
+                         const uint8_t* lut, const float* mask, int32_t thickness, uint32_t outline_rgb, double alpha,
+                         int32_t ho, int32_t wo, int32_t bgr, uint8_t* out, uint16_t* out_u16, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Tiled inference for inputs larger than the network's native 518 x 518 (the reference squashes every
