@@ -227,7 +227,10 @@ __global__ __launch_bounds__(256, 2) void attention_kernel_v3(const op_t* __rest
             const op_t m16 = (op_t)(m_run + mx);
             const float m_new = mv ? (float)m16 : m_run;
             const float delta = m_new - m_run;
-            const float alpha = __builtin_amdgcn_exp2f(-delta);
+            // alpha clamped to [0, 1] (the v_exp_f32's own output modifier: no instruction added).  A later tile never has delta < 0; tile 0
+            // moves m from its initial 0 to the tile's maximum, down as well as up, while O and l are still zero: nothing to rescale, but below
+            // -128 the bare exp2(-delta) is inf and 0 * inf = NaN stays in O and l for the rest of the row.
+            const float alpha = __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(-delta), 0.0f, 1.0f);
             l_run *= alpha;
             m_run = m_new;
             if (hi == 0) qx[0] = (op_t)(-m_new);
@@ -532,7 +535,11 @@ __global__ __launch_bounds__(256, ADA_ATTN_OCC) void attention_kernel_mix(const 
                 const bool mv = (j == 0) || (mx > RESCALE_THR);
                 const float m_new = mv ? m_run + mx : m_run;
                 const float delta = m_new - m_run;
-                const float alpha = __builtin_amdgcn_exp2f(-delta);
+                // alpha clamped to [0, 1] (folds into the v_exp_f32's output modifier: no instruction added, the listing is otherwise the one
+                // without the clamp, where a select on j == 0 adds a v_cndmask and shifts the loop).  A later tile never has delta < 0; tile 0 moves m from its
+                // initial 0 to the tile's maximum, down as well as up, while O, l and P(-1) are still zero: nothing to rescale, but below -128 the
+                // bare exp2(-delta) is inf and 0 * inf = NaN stays in O, lacc and P for the rest of the row.
+                const float alpha = __builtin_amdgcn_fmed3f(__builtin_amdgcn_exp2f(-delta), 0.0f, 1.0f);
                 const op_t alpha_op = (op_t)alpha;     // alpha <= 1; P(j-1) <= 2^8: no overflow
                 if constexpr (MROW) {   // row 0 of the row-sum tile belongs to this lane's query (lanes 0-15), row 1 to the query 16 lanes up
                     lacc[0] *= alpha;

@@ -172,6 +172,12 @@ int ada_igemm(const ada_igemm_args* args, void* stream);
  *   out: [B*N, heads*64] op-typed (the "transpose(1,2).reshape(B,N,C)" layout of :59).
  *   The N x N score matrix is never materialised: K/V tiles of 64 keys are staged through LDS,
  *   softmax runs online in fp32 registers.
+ *   Score range: q k^T (log2 units, after the pre-scale) is tested for +-4096 with any placement over the key tiles -- every
+ *   key, the first tile only, some query rows only, a maximum that climbs tile by tile (tests/test_gpu_attention_values.py);
+ *   nothing upstream bounds it.  The shipped kernel keeps the running maximum in fp32.  The alternate kernel
+ *   (ada_debug_set_attention_variant(3)) keeps it in the operand type and so has a hard limit the shipped one has not: the
+ *   maximum is rounded to the operand type's grid (fp16: steps of 2 below 4096 and of 4 above, nothing beyond 65504) and P
+ *   carries what the rounding leaves.
  * ---------------------------------------------------------------------------------------- */
 int ada_attention_fwd(const void* qkv, void* out, int32_t batch, int32_t n_tokens, int32_t heads,
                       void* stream);
