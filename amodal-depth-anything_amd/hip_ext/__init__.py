@@ -28,7 +28,7 @@ ACT_NONE, ACT_SIGMOID, ACT_RELU = 0, 1, 2
 EXPORTS = (
     "ada_abi_version", "ada_operand_dtype", "ada_last_error", "ada_igemm", "ada_attention_fwd", "ada_attention_ex",
     "ada_pos_embed_resize", "ada_layernorm_fwd", "ada_layernorm_ex", "ada_patchify", "ada_write_cls", "ada_bilinear_fwd", "ada_selftest",
-    "ada_minmax_fwd", "ada_depth_stats_fwd", "ada_token_diversity_fwd", "ada_normalize_fwd", "ada_blend_fwd", "ada_depth_eval_fwd", "ada_tile_blend_fwd", "ada_dpt_tail_fwd", "ada_tapsum_resize_fwd",
+    "ada_minmax_fwd", "ada_depth_stats_fwd", "ada_token_diversity_fwd", "ada_normalize_fwd", "ada_blend_fwd", "ada_depth_eval_fwd", "ada_protocol_fit_fwd", "ada_protocol_eval_fwd", "ada_tile_blend_fwd", "ada_dpt_tail_fwd", "ada_tapsum_resize_fwd",
     "ada_image_prep_fwd", "ada_depth_resize_fwd",
     "ada_photo_prep_fwd", "ada_mask_prep_fwd", "ada_nearest_resize_fwd", "ada_blend_ex", "ada_depth_render_fwd",
     "ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_last_tile",
@@ -39,6 +39,11 @@ EXPORTS = (
 EVAL_N, EVAL_SUM_P, EVAL_SUM_G, EVAL_SUM_PP, EVAL_SUM_PG, EVAL_ABS_REL, EVAL_SQ_REL, EVAL_SQ, EVAL_LOG_SQ, EVAL_LOG, \
     EVAL_LOG10_ABS, EVAL_D1, EVAL_D2, EVAL_D3, EVAL_INV_SQ = range(15)
 EVAL_NSUM = 16
+# ada_protocol_fit_fwd / ada_protocol_eval_fwd: columns of a fit row (ADA_FIT_*), pixels per chunk and fp64 words of workspace per chunk
+FIT_N, FIT_SUM_P, FIT_SUM_O, FIT_SUM_PP, FIT_SUM_PO, FIT_MIN_P, FIT_MAX_P, FIT_N_VISIBLE, FIT_N_WHOLE, FIT_SCALE, FIT_SHIFT = range(11)
+FIT_NCOL = 12
+PROTOCOL_CHUNK = 4096
+PROTOCOL_WS_DOUBLES = 32
 
 
 class IgemmArgs(ctypes.Structure):
@@ -145,6 +150,11 @@ def load(path: Optional[str] = None):
     lib.ada_tapsum_resize_fwd.restype = c_int
     lib.ada_depth_eval_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_float, c_float, c_void_p, c_void_p]
     lib.ada_depth_eval_fwd.restype = c_int
+    lib.ada_protocol_fit_fwd.argtypes = [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.ada_protocol_fit_fwd.restype = c_int
+    lib.ada_protocol_eval_fwd.argtypes = [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                          c_int64, c_void_p]
+    lib.ada_protocol_eval_fwd.restype = c_int
     lib.ada_image_prep_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32, c_int32,
                                        ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p, c_void_p]
     lib.ada_image_prep_fwd.restype = c_int
@@ -430,6 +440,69 @@ def depth_eval(pred, gt, mask=None, scale_shift=None, clip=None) -> torch.Tensor
                                      _dev(mask, "mask", torch.uint8) if mask is not None else None, B, n,
                                      _dev(scale_shift, "scale_shift", torch.float32) if scale_shift is not None else None,
                                      lo, hi, _dev(sums, "sums", torch.float64), _stream()), "ada_depth_eval_fwd")
+    return sums
+
+
+def protocol_workspace_bytes(batch: int, h: int, w: int) -> int:
+    """Bytes of workspace ada_protocol_fit_fwd / ada_protocol_eval_fwd ask for (include/ada_hip.h)."""
+    return batch * ((h * w + PROTOCOL_CHUNK - 1) // PROTOCOL_CHUNK) * PROTOCOL_WS_DOUBLES * 8
+
+
+def _protocol_maps(who, pred, maps):
+    """pred fp32 [B, hp, wp]; every (name, tensor, dtype, optional) of ``maps`` [B, h, w] with one (h, w), contiguous, on pred's device (bool masks are
+    viewed as uint8).  Returns (B, hp, wp, h, w, device pointers in the order of ``maps``)."""
+    if not isinstance(pred, torch.Tensor) or pred.dim() != 3 or not pred.is_contiguous():
+        raise HipExtError(f"{who}: pred must be a contiguous [B, hp, wp] tensor, got {tuple(getattr(pred, 'shape', ()))}")
+    _dev(pred, "pred", torch.float32)
+    B, hp, wp = pred.shape
+    shape, ptrs = None, []
+    for name, t, dtype, optional in maps:
+        if t is None and optional:
+            ptrs.append(None)
+            continue
+        if isinstance(t, torch.Tensor) and t.dtype == torch.bool and dtype == torch.uint8 and t.is_contiguous():
+            t = t.view(torch.uint8)
+        ptrs.append(_dev(t, name, dtype))
+        if t.dim() != 3 or not t.is_contiguous() or t.shape[0] != B or t.device != pred.device:
+            raise HipExtError(f"{who}: {name} must be a contiguous [{B}, h, w] tensor on {pred.device}, got {tuple(t.shape)} on {t.device}")
+        shape = shape or tuple(t.shape)
+        if tuple(t.shape) != shape:
+            raise HipExtError(f"{who}: {name} is {tuple(t.shape)}, the other maps are {shape}")
+    return B, hp, wp, shape[1], shape[2], ptrs
+
+
+def _protocol_workspace(who, workspace, need, device):
+    if workspace is None:
+        return torch.empty(need // 8, dtype=torch.float64, device=device)
+    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != device:
+        raise HipExtError(f"{who}: workspace must be a contiguous tensor on {device}")
+    return workspace
+
+
+def protocol_fit(pred, observation, visible, whole, workspace=None) -> torch.Tensor:
+    """Fit rows fp64 [B, FIT_NCOL] of the prediction (fp32 [B, hp, wp], gathered to the maps' size by ATen's nearest rule) onto ``observation`` (fp32
+    [B, h, w]) over ``visible`` (uint8 / bool [B, h, w]), with the pixel counts of ``visible`` and ``whole`` (ada_protocol_fit_fwd).  ``workspace``:
+    any contiguous device tensor of at least protocol_workspace_bytes(B, h, w) bytes, allocated when None."""
+    B, hp, wp, h, w, (po, pv, pw) = _protocol_maps("protocol_fit", pred, (("observation", observation, torch.float32, False),
+                                                                           ("visible", visible, torch.uint8, False), ("whole", whole, torch.uint8, False)))
+    ws = _protocol_workspace("protocol_fit", workspace, protocol_workspace_bytes(B, h, w), pred.device)
+    fit = torch.empty(B, FIT_NCOL, dtype=torch.float64, device=pred.device)
+    _check(load().ada_protocol_fit_fwd(pred.data_ptr(), hp, wp, po, pv, pw, B, h, w, fit.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+           "ada_protocol_fit_fwd")
+    return fit
+
+
+def protocol_eval(pred, gt, region, valid, fit, eps=1e-5, workspace=None) -> torch.Tensor:
+    """fp64 [B, 2, EVAL_NSUM]: the EVAL_* sums over region != 0 && valid != 0 (``valid`` None: every pixel) of gt + eps against pred + eps (row 0)
+    and against pred * scale + shift + eps with the fit rows' scale / shift (row 1) (ada_protocol_eval_fwd).  Shapes and workspace as protocol_fit."""
+    B, hp, wp, h, w, (pg, pr, pv) = _protocol_maps("protocol_eval", pred, (("gt", gt, torch.float32, False), ("region", region, torch.uint8, False),
+                                                                            ("valid", valid, torch.uint8, True)))
+    if not isinstance(fit, torch.Tensor) or tuple(fit.shape) != (B, FIT_NCOL) or not fit.is_contiguous() or fit.device != pred.device:
+        raise HipExtError(f"protocol_eval: fit must be a contiguous [{B}, {FIT_NCOL}] tensor on {pred.device}, got {tuple(getattr(fit, 'shape', ()))}")
+    ws = _protocol_workspace("protocol_eval", workspace, protocol_workspace_bytes(B, h, w), pred.device)
+    sums = torch.empty(B, 2, EVAL_NSUM, dtype=torch.float64, device=pred.device)
+    _check(load().ada_protocol_eval_fwd(pred.data_ptr(), hp, wp, pg, pr, pv, _dev(fit, "fit", torch.float64), float(eps), B, h, w, sums.data_ptr(), ws.data_ptr(),
+                                        ws.numel() * ws.element_size(), _stream()), "ada_protocol_eval_fwd")
     return sums
 
 

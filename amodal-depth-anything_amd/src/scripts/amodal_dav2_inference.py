@@ -11,6 +11,10 @@ when a ground-truth depth directory is given, evaluates on the device: per-sampl
     python -m src.scripts.amodal_dav2_inference --trained_checkpoint DIR --occ_image_dir A --whole_mask_dir B \
         --observation_depth_dir C --output_dir OUT [--gt_depth_dir D] [--split_file val.txt] [--batch_size 32]
 
+``--protocol paper --visible_mask_dir E [--invisible_mask_dir F]`` evaluates by the paper's protocol instead (src/util/validation.py: fit onto the
+observation over the visible mask, metrics over the invisible part, raw and aligned, easy / mid / diff buckets, per-metric NaN skip);
+``metrics.json`` then holds the eight groups and their per-metric counts.
+
 Multi-GPU: launch one process per GPU (``python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 -m
 src.scripts.amodal_dav2_inference ...``).  The sample list is sharded contiguously over the ranks (hip_ext.parallel.shard_range),
 each rank writes its own PNGs, and the per-sample metric sums are combined with one all-reduce at the end.
@@ -46,7 +50,15 @@ def _resize(t: torch.Tensor) -> torch.Tensor:   # InterpolationMode.NEAREST_EXAC
     return F.interpolate(t[None].float(), size=RESIZE_HW, mode="nearest-exact")[0]
 
 
-def load_sample(sid: str, occ_image_dir: str, whole_mask_dir: str, observation_depth_dir: str, gt_depth_dir: Optional[str]) -> Dict[str, torch.Tensor]:
+def _load_mask(path: str) -> torch.Tensor:
+    m = np.asarray(Image.open(path))
+    if m.ndim == 3:
+        m = m[..., 0]
+    return _resize(torch.from_numpy(m.astype(np.float32))[None]) > 0                                          # [1,518,518] bool
+
+
+def load_sample(sid: str, occ_image_dir: str, whole_mask_dir: str, observation_depth_dir: str, gt_depth_dir: Optional[str],
+                visible_mask_dir: Optional[str] = None, invisible_mask_dir: Optional[str] = None) -> Dict[str, torch.Tensor]:
     img = np.asarray(Image.open(os.path.join(occ_image_dir, f"{sid}_occlusion.png")).convert("RGB"))
     image = _resize(torch.from_numpy(img.transpose(2, 0, 1).astype(np.float32)) / 255)                       # [3,518,518] in [0,1]
     obs = np.asarray(Image.open(os.path.join(observation_depth_dir, f"{sid}_depth.png"))).astype(np.float32) / 65535
@@ -59,15 +71,28 @@ def load_sample(sid: str, occ_image_dir: str, whole_mask_dir: str, observation_d
     if gt_depth_dir:
         gt = np.asarray(Image.open(os.path.join(gt_depth_dir, f"{sid}_depth.png"))).astype(np.float32) / 65535
         out["gt_depth"] = _resize(torch.from_numpy(gt)[None])
+    if visible_mask_dir:     # pix2gestalt_eval.py:204-207
+        out["visible_mask"] = _load_mask(os.path.join(visible_mask_dir, f"{sid}_visible_mask.png"))
+    if invisible_mask_dir:
+        out["invisible_mask"] = _load_mask(os.path.join(invisible_mask_dir, f"{sid}_invisible_mask.png"))
     return out
 
 
 def run(model: Callable, ids: List[str], occ_image_dir: str, whole_mask_dir: str, observation_depth_dir: str, output_dir: str,
         gt_depth_dir: Optional[str] = None, batch_size: int = 32, device: str = "cuda", evaluate: Optional[Callable] = None,
-        group=None) -> Dict[str, float]:
+        group=None, protocol: str = "legacy", visible_mask_dir: Optional[str] = None, invisible_mask_dir: Optional[str] = None) -> Dict[str, float]:
     """Runs the model over ``ids`` in batches, writes ``{output_dir}/amodal_depth/{id}_depth.png`` (uint16, depth * 65535, :124-125)
     and returns the per-sample metrics averaged over the samples when ground truth is available.  ``evaluate(pred, gt, mask) -> dict``
-    (applied to one sample at a time) defaults to the device path."""
+    (applied to one sample at a time) defaults to the device path.
+
+    ``protocol="paper"`` (needs ``gt_depth_dir`` and ``visible_mask_dir``): the evaluation of src/util/validation.py; returns its eight groups
+    plus ``"counts"`` (per group and metric, the samples that entered the mean).  ``evaluate`` is then a batch evaluator with the signature of
+    ``validation.evaluate_batch(pred, gt, observation, whole, visible, invisible, valid)``."""
+    if protocol not in ("legacy", "paper"):
+        raise ValueError(f"protocol must be 'legacy' or 'paper', got {protocol!r}")
+    paper = protocol == "paper"
+    if paper and not (gt_depth_dir and visible_mask_dir):
+        raise ValueError("protocol='paper' needs gt_depth_dir and visible_mask_dir")
     out_depth = os.path.join(output_dir, "amodal_depth")
     os.makedirs(out_depth, exist_ok=True)
     # Metrics follow the reference's evaluation semantics -- one sample at a time (its loader runs batch size 1), then the mean over
@@ -75,7 +100,11 @@ def run(model: Callable, ids: List[str], occ_image_dir: str, whole_mask_dir: str
     # in the batch).  ``evaluate(pred, gt, mask) -> dict`` is applied per sample; the default computes the per-image sums of the
     # whole batch in one device pass and derives each sample's metrics from its own row.
     per_sample = None
-    if gt_depth_dir and evaluate is None:
+    if paper:
+        from src.util import validation
+        tracker = validation.ValidationTracker()
+        evaluate = evaluate or validation.evaluate_batch
+    elif gt_depth_dir and evaluate is None:
         from src.util import alignment, metric
 
         def per_sample(pred, gt, mask):
@@ -97,7 +126,10 @@ def run(model: Callable, ids: List[str], occ_image_dir: str, whole_mask_dir: str
     count = 0
     for i in range(0, len(ids), batch_size):
         chunk = ids[i:i + batch_size]
-        samples = [load_sample(s, occ_image_dir, whole_mask_dir, observation_depth_dir, gt_depth_dir) for s in chunk]
+        if paper:
+            samples = [load_sample(s, occ_image_dir, whole_mask_dir, observation_depth_dir, gt_depth_dir, visible_mask_dir, invisible_mask_dir) for s in chunk]
+        else:
+            samples = [load_sample(s, occ_image_dir, whole_mask_dir, observation_depth_dir, gt_depth_dir) for s in chunk]
         image = torch.stack([s["image"] for s in samples]).to(device)
         mask = torch.stack([s["whole_mask"] for s in samples]).to(device)
         obs = torch.stack([s["observation"] for s in samples]).to(device)
@@ -107,13 +139,25 @@ def run(model: Callable, ids: List[str], occ_image_dir: str, whole_mask_dir: str
         d16 = (depth.detach().float().cpu().numpy() * 65535.0).astype(np.uint16)
         for sid, arr in zip(chunk, d16):
             Image.fromarray(arr).save(os.path.join(out_depth, f"{sid}_depth.png"))
-        if gt_depth_dir:
+        if paper:
+            stack = lambda k: torch.stack([s[k] for s in samples]).to(device).reshape(len(chunk), *RESIZE_HW)      # noqa: E731
+            gt = stack("gt_depth")
+            for res in evaluate(depth.float(), gt, obs.reshape(len(chunk), *RESIZE_HW), mask.reshape(len(chunk), *RESIZE_HW), stack("visible_mask"),
+                                stack("invisible_mask") if invisible_mask_dir else None, gt > 0):
+                tracker.update(res)
+        elif gt_depth_dir:
             gt = torch.stack([s["gt_depth"] for s in samples]).to(device).reshape(len(chunk), *RESIZE_HW)
             valid = mask.reshape(len(chunk), *RESIZE_HW) & (gt > 0)
             for res in per_sample(depth.float(), gt, valid):
                 for k, v in res.items():
                     totals[k] = totals.get(k, 0.0) + v
             count += len(chunk)
+    if paper:
+        if world > 1:   # one fixed-length vector of totals and counts: the group and metric names are fixed
+            vec = torch.tensor(tracker.state_vector(), dtype=torch.float64, device=device if dist.get_backend(group) == "nccl" else "cpu")
+            dist.all_reduce(vec, group=group)
+            tracker.load_state_vector(vec.tolist())
+        return {**tracker.result(), "counts": tracker.counts()}
     if world > 1 and gt_depth_dir:
         # metric names are fixed by the evaluator, so every rank (also one with an empty share) builds the same vector
         keys = sorted(totals) if totals else None
@@ -138,6 +182,10 @@ def main(argv=None):
     ap.add_argument("--observation_depth_dir", required=True)
     ap.add_argument("--gt_depth_dir", default=None)
     ap.add_argument("--split_file", default=None)
+    ap.add_argument("--protocol", choices=("legacy", "paper"), default="legacy",
+                    help="legacy: fit onto the gt inside the whole mask, one mean; paper: the reference's validation protocol (src/util/validation.py)")
+    ap.add_argument("--visible_mask_dir", default=None, help="{id}_visible_mask.png (--protocol paper)")
+    ap.add_argument("--invisible_mask_dir", default=None, help="{id}_invisible_mask.png; default: whole & ~visible")
     ap.add_argument("--output_dir", required=True)
     ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--device", default="cuda")
@@ -164,7 +212,11 @@ def main(argv=None):
         model.load_state_dict(sd, strict=True)
     model = model.eval().to(a.device)
     ids = sample_ids(a.occ_image_dir, a.split_file)
-    metrics = run(model, ids, a.occ_image_dir, a.whole_mask_dir, a.observation_depth_dir, a.output_dir, a.gt_depth_dir, a.batch_size, a.device)
+    if a.protocol == "paper":
+        metrics = run(model, ids, a.occ_image_dir, a.whole_mask_dir, a.observation_depth_dir, a.output_dir, a.gt_depth_dir, a.batch_size, a.device,
+                      protocol="paper", visible_mask_dir=a.visible_mask_dir, invisible_mask_dir=a.invisible_mask_dir)
+    else:
+        metrics = run(model, ids, a.occ_image_dir, a.whole_mask_dir, a.observation_depth_dir, a.output_dir, a.gt_depth_dir, a.batch_size, a.device)
     if metrics and rank == 0:
         with open(os.path.join(a.output_dir, "metrics.json"), "w") as f:
             json.dump(metrics, f, indent=1)

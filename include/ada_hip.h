@@ -344,6 +344,46 @@ int ada_depth_eval_fwd(const float* pred, const float* gt, const uint8_t* mask, 
                        double* sums, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The paper's evaluation protocol (reference: src/trainer/discriminative_trainer.py:496-613, src/scripts/pix2gestalt_eval.py:200-297): the
+ * prediction is fitted onto the OBSERVATION over the VISIBLE mask, and the metrics are taken over the invisible region, raw and aligned.
+ * Every map is [B, h, w] contiguous at the evaluation size; the prediction is fp32 [B, hp, wp] and is gathered inside both passes by ATen's
+ * legacy nearest rule, per axis  src = min((int)floorf(dst * ((float)in / out)), in - 1)  (the identity for equal sizes).  Masks are uint8,
+ * non-zero = inside.
+ *   ada_protocol_fit_fwd   fit fp64 [B, ADA_FIT_NCOL] (overwritten), indexed by ADA_FIT_*: over visible != 0 the count, sum p, sum o, sum p p,
+ *                          sum p o, min p, max p (+inf / -inf without a visible pixel); the counts of visible != 0 and of whole != 0 (the
+ *                          difficulty bucket's ratio); scale and shift minimising sum (p scale + shift - o)^2, solved in fp64 from the normal
+ *                          equations.  Two rank-deficient systems get numpy.linalg.lstsq's minimum-norm answer in closed form: no visible
+ *                          pixel (0, 0); every visible p equal to c, i.e. min == max, (c m / (c c + 1), m / (c c + 1)) with m the mean o.
+ *   ada_protocol_eval_fwd  sums fp64 [B, 2, ADA_EVAL_NSUM] (overwritten), the ADA_EVAL_* sums over region != 0 && valid != 0 (valid NULL:
+ *                          every pixel valid) of g = gt + eps against  row 0: p = pred + eps;  row 1: p = (pred * scale) + shift + eps  with
+ *                          scale / shift the fp32 roundings of the fit row's (the product is rounded before the sum, as in ada_blend_ex).  No
+ *                          clamp: a negative p turns exactly the three log sums into NaN.
+ * Neither uses atomics.  An image is cut into ceil(h w / ADA_PROTOCOL_CHUNK) chunks, each reduced by one workgroup in a fixed order, and the
+ * chunk partials are added in index order: an image's result is bit-identical from run to run and alone or inside any batch.
+ *   workspace  device memory, 8-byte aligned, at least  batch * ceil(h w / ADA_PROTOCOL_CHUNK) * ADA_PROTOCOL_WS_DOUBLES * 8  bytes (checked);
+ *              contents are scratch, and the two calls may share it (they run in stream order).
+ * ---------------------------------------------------------------------------------------- */
+#define ADA_PROTOCOL_CHUNK 4096      /* pixels per chunk */
+#define ADA_PROTOCOL_WS_DOUBLES 32   /* fp64 words of workspace per chunk */
+#define ADA_FIT_N 0           /* visible pixels */
+#define ADA_FIT_SUM_P 1       /* sum p */
+#define ADA_FIT_SUM_O 2       /* sum o */
+#define ADA_FIT_SUM_PP 3      /* sum p*p */
+#define ADA_FIT_SUM_PO 4      /* sum p*o */
+#define ADA_FIT_MIN_P 5
+#define ADA_FIT_MAX_P 6
+#define ADA_FIT_N_VISIBLE 7   /* #{visible != 0} */
+#define ADA_FIT_N_WHOLE 8     /* #{whole != 0} */
+#define ADA_FIT_SCALE 9
+#define ADA_FIT_SHIFT 10
+#define ADA_FIT_NCOL 12
+int ada_protocol_fit_fwd(const float* pred, int32_t hp, int32_t wp, const float* observation, const uint8_t* visible, const uint8_t* whole,
+                         int32_t batch, int32_t h, int32_t w, double* fit, void* workspace, int64_t workspace_bytes, void* stream);
+int ada_protocol_eval_fwd(const float* pred, int32_t hp, int32_t wp, const float* gt, const uint8_t* region, const uint8_t* valid,
+                          const double* fit, float eps, int32_t batch, int32_t h, int32_t w, double* sums, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Device-side glue of the two-model pipeline of infer.py (kept in HBM instead of bouncing through numpy):
  *   ada_minmax_fwd     per-image min / max of a [B, n] fp32 map -> minmax[B, 2]          (infer.py:22)
  *   ada_normalize_fwd  norm = (d - min) / (max - min) and/or obs = norm * 2 - 1          (infer.py:22,92)
