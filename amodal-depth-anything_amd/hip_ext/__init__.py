@@ -31,6 +31,7 @@ EXPORTS = (
     "ada_minmax_fwd", "ada_depth_stats_fwd", "ada_token_diversity_fwd", "ada_normalize_fwd", "ada_blend_fwd", "ada_depth_eval_fwd", "ada_protocol_fit_fwd", "ada_protocol_eval_fwd", "ada_tile_blend_fwd", "ada_dpt_tail_fwd", "ada_tapsum_resize_fwd",
     "ada_image_prep_fwd", "ada_depth_resize_fwd",
     "ada_photo_prep_fwd", "ada_mask_prep_fwd", "ada_nearest_resize_fwd", "ada_blend_ex", "ada_depth_render_fwd",
+    "ada_pil_resize_u8_fwd", "ada_label_combine_fwd",
     "ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_last_tile",
     "ada_debug_set_timestamps", "ada_debug_set_attention_variant", "ada_debug_count_saturated",
 )
@@ -44,6 +45,9 @@ FIT_N, FIT_SUM_P, FIT_SUM_O, FIT_SUM_PP, FIT_SUM_PO, FIT_MIN_P, FIT_MAX_P, FIT_N
 FIT_NCOL = 12
 PROTOCOL_CHUNK = 4096
 PROTOCOL_WS_DOUBLES = 32
+# ada_pil_resize_u8_fwd's filters (Pillow's own numbers) and ada_label_combine_fwd's casts
+PIL_NEAREST, PIL_BICUBIC = 0, 3
+LABEL_WRAP, LABEL_CLIP = 0, 1
 
 
 class IgemmArgs(ctypes.Structure):
@@ -171,6 +175,12 @@ def load(path: Optional[str] = None):
     lib.ada_depth_render_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_int32, ctypes.c_uint32,
                                          c_double, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
     lib.ada_depth_render_fwd.restype = c_int
+    lib.ada_pil_resize_u8_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                                          c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.ada_pil_resize_u8_fwd.restype = c_int
+    lib.ada_label_combine_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]
+    lib.ada_label_combine_fwd.restype = c_int
     for name in ("ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_set_attention_variant"):
         getattr(lib, name).argtypes = [c_int]
         getattr(lib, name).restype = None
@@ -588,6 +598,50 @@ def depth_render(depth, lut, ho, wo, out=None, out_u16=None, *, minmax=None, vmi
                                        _dev(lut, "lut", torch.uint8), _opt(mask, "mask", torch.float32), int(thickness), int(outline_rgb), float(alpha),
                                        int(ho), int(wo), int(bool(bgr)), _opt(out, "out", torch.uint8), _opt(out_u16, "out_u16", torch.uint16), _stream()),
            "ada_depth_render_fwd")
+
+
+def pil_resize_u8(src, batch, hi, wi, channels, row_pitch, image_stride, ho, wo, filter=PIL_BICUBIC, tables_x=None, tables_y=None, tmp=None,
+                  out_u8=None, out_f32=None, out_mask=None):
+    """uint8 HWC images (1 or 3 channels; rows ``row_pitch`` bytes apart, images ``image_stride`` bytes apart) -> Pillow's Image.resize bytes
+    ``out_u8`` [batch, ho, wo, channels], ``out_f32`` = bytes / 255 planar [batch, channels, ho, wo], ``out_mask`` uint8 = bytes > 0 [batch, ho, wo]
+    (ada_pil_resize_u8_fwd).  ``tables_x`` / ``tables_y``: (bounds, kk, ksize) with device int32 tensors per resized axis for PIL_BICUBIC (None for an
+    axis that keeps its size); ``tmp``: uint8 workspace of batch * hi * wo * channels bytes when both axes are resized."""
+    n = batch * ho * wo
+    for name, t, need in (("out_u8", out_u8, n * channels), ("out_f32", out_f32, n * channels), ("out_mask", out_mask, n)):
+        if t is not None and (not isinstance(t, torch.Tensor) or not t.is_contiguous() or t.numel() != need):
+            raise HipExtError(f"pil_resize_u8: {name} must be a contiguous tensor of {need} elements, got {tuple(getattr(t, 'shape', ()))}")
+    _check_src_extent("pil_resize_u8", src, (batch - 1) * image_stride + (hi - 1) * row_pitch + wi * channels)
+    ptrs = []
+    for axis, tab, n_out in (("x", tables_x, wo), ("y", tables_y, ho)):
+        if tab is None:
+            ptrs += [None, None, 0]
+            continue
+        bounds, kk, ksize = tab
+        if bounds.numel() != 2 * n_out or kk.numel() != n_out * ksize or not (bounds.is_contiguous() and kk.is_contiguous()):
+            raise HipExtError(f"pil_resize_u8: tables_{axis} must be contiguous [{n_out}, 2] and [{n_out}, {ksize}], got {tuple(bounds.shape)} {tuple(kk.shape)}")
+        ptrs += [_dev(bounds, f"bounds_{axis}", torch.int32), _dev(kk, f"kk_{axis}", torch.int32), int(ksize)]
+    _check(load().ada_pil_resize_u8_fwd(_dev(src, "src", torch.uint8), batch, hi, wi, channels, row_pitch, image_stride, ho, wo, int(filter), *ptrs,
+                                        _opt(tmp, "tmp", torch.uint8), tmp.numel() if tmp is not None else 0, _opt(out_u8, "out_u8", torch.uint8),
+                                        _opt(out_f32, "out_f32", torch.float32), _opt(out_mask, "out_mask", torch.uint8), _stream()), "ada_pil_resize_u8_fwd")
+
+
+def label_combine(whole, occ, whole_mask, scale_shift, out_u16, out_f32=None, out_of_range=None, overflow=LABEL_WRAP):
+    """whole, occ fp32 [P, h, w], whole_mask uint8 [P, h, w], scale_shift fp32 [P, 2] -> out_u16 uint16 [P, ho, wo] (Pillow's NEAREST gather of the
+    quantised paste), optionally out_f32 fp32 [P, h, w] (the paste) and out_of_range int32 [P, ho] (ada_label_combine_fwd).  All contiguous, one device."""
+    if not isinstance(whole, torch.Tensor) or whole.dim() != 3 or not isinstance(out_u16, torch.Tensor) or out_u16.dim() != 3 or out_u16.shape[0] != whole.shape[0]:
+        raise HipExtError(f"label_combine: whole [P, h, w] and out_u16 [P, ho, wo] required, got {tuple(getattr(whole, 'shape', ()))} {tuple(getattr(out_u16, 'shape', ()))}")
+    P, h, w = whole.shape
+    ho, wo = out_u16.shape[1:]
+    for name, t, shape in (("whole", whole, (P, h, w)), ("occ", occ, (P, h, w)), ("whole_mask", whole_mask, (P, h, w)), ("scale_shift", scale_shift, (P, 2)),
+                           ("out_u16", out_u16, (P, ho, wo)), ("out_f32", out_f32, (P, h, w)), ("out_of_range", out_of_range, (P, ho))):
+        if t is None and name in ("out_f32", "out_of_range"):
+            continue
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or not t.is_contiguous() or t.device != whole.device:
+            raise HipExtError(f"label_combine: {name} must be a contiguous {shape} tensor on {whole.device}, got {tuple(getattr(t, 'shape', ()))}")
+    _check(load().ada_label_combine_fwd(_dev(whole, "whole", torch.float32), _dev(occ, "occ", torch.float32), _dev(whole_mask, "whole_mask", torch.uint8),
+                                        _dev(scale_shift, "scale_shift", torch.float32), P, h, w, ho, wo, int(overflow), _dev(out_u16, "out_u16", torch.uint16),
+                                        _opt(out_f32, "out_f32", torch.float32), _opt(out_of_range, "out_of_range", torch.int32), _stream()),
+           "ada_label_combine_fwd")
 
 
 # --- tuning / diagnostic hooks (include/ada_hip.h, last section) ---------------------------------

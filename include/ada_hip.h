@@ -502,6 +502,58 @@ int ada_depth_render_fwd(const float* depth, int32_t batch, int32_t hi, int32_t 
                          int32_t ho, int32_t wo, int32_t bgr, uint8_t* out, uint16_t* out_u16, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The ADIW pseudo-label generator (reference src/scripts/sam_pl_gen_dav2.py), which prepares every photo and mask with Pillow on the host
+ * (Image.open(fp).convert('RGB').resize((518, 518)), lines 28, 93-98) and quantises the label with numpy (lines 115-121).  Additions under ABI 10.
+ *   ada_pil_resize_u8_fwd   Pillow's ImagingResample for 8-bit pixels with filter BICUBIC (libImaging/Resample.c), and its NEAREST, byte for byte.
+ *     src      uint8 HWC [batch][hi][wi][channels], channels 1 (L) or 3 (RGB); rows row_pitch_bytes apart, images image_stride_bytes apart, as
+ *              ada_image_prep_fwd: a crop is read in place.
+ *     filter   ADA_PIL_BICUBIC: per resized axis the caller passes DEVICE int32 tables, bounds [n_out][2] = (xmin, n) and kk [n_out][ksize], computed
+ *              on the host in double (hip_ext/labels.py pil_coeffs) by Pillow's precompute_coeffs / normalize_coeffs_8bpc:
+ *                scale = n_in / n_out;  fs = max(scale, 1.0);  support = 2.0 * fs;  ksize = (int)ceil(support) * 2 + 1;  ss = 1.0 / fs
+ *                center = (xx + 0.5) * scale;  xmin = max((int)(center - support + 0.5), 0);  xmax = min((int)(center + support + 0.5), n_in);  n = xmax - xmin
+ *                w[x] = f((x + xmin - center + 0.5) * ss), x < n;  f(t) with a = -0.5:  |t| < 1: ((a + 2) t - (a + 3)) t t + 1;  |t| < 2: (((t - 5) t + 8) t - 4) a;  else 0
+ *                the weights are divided by their sum (accumulated in index order; not when it is 0), then quantised as (int)(w * 2^22 + 0.5), or - 0.5
+ *                for a negative w; entries past n are 0.  The support grows with the down-scale factor: 19 taps per axis for 2250 -> 518.
+ *              The horizontal pass runs first, into the uint8 intermediate tmp [batch][hi][wo][channels] (the caller's workspace, tmp_bytes checked;
+ *              needed only when both axes are resized), then the vertical pass.  Each pass:  acc = 2^21 + sum k[x] * pixel[xmin + x]  in int32 (Pillow's
+ *              int), out = clamp(acc >> 22, 0, 255), the shift arithmetic (a negative sum clamps to 0).  The intermediate is ROUNDED TO uint8 between
+ *              the passes, as Pillow rounds it: the passes are not fused at higher precision.  A pass whose n_in == n_out is skipped, as Pillow skips
+ *              it (its tables may be NULL); with both skipped the pixels are copied.  The kernels clamp (xmin, n) to the axis.
+ *              ADA_PIL_NEAREST (no tables, no tmp): per axis  src = min((int)floor((dst + 0.5) * ((double)n_in / n_out)), n_in - 1)  in double.
+ *     outputs  any non-empty subset, none aliasing src:
+ *                out_u8    HWC [batch][ho][wo][channels]: Pillow's bytes
+ *                out_f32   planar [batch, channels, ho, wo]: v / 255.f, IEEE division = (float)((double)v / 255.0) for all 256 values -- np.array(im) / 255
+ *                          cast to float32 (line 29-31).  Channel order kept: R, G, B planes for a convert('RGB') photo.
+ *                out_mask  uint8 [batch][ho][wo] = v > 0 (lines 94, 98), channels == 1 only
+ *   ada_label_combine_fwd   lines 115-117 and 121 in one launch.  whole, occ: fp32 [P, h, w], already min-max normalised; whole_mask: uint8 [P, h, w],
+ *              non-zero = inside; scale_shift: DEVICE fp32 [P, 2].  No output may alias an input.
+ *                v = whole_mask ? (whole * scale) + shift : occ   in fp32, the product rounded before the sum (no FMA), as in ada_blend_ex
+ *                t = v * 65535.f
+ *                ADA_LABEL_WRAP  numpy's astype(np.uint16) on x86-64, the reference's cast: NaN or |t| >= 2^31 gives 0, otherwise the low 16 bits of
+ *                                (int32)trunc(t):  -3.7 -> 65533, 65536.0 -> 0, 65537.9 -> 1, 70000.5 -> 4464, NaN -> 0, 1e10 -> 0.  (The hardware's
+ *                                conversion saturates; the rule is written out.)
+ *                ADA_LABEL_CLIP  trunc after clamping t to [0, 65535]; NaN gives 0.
+ *     out_u16       uint16 [P, ho, wo]: output pixel (dy, dx) shows source pixel (sy, sx) by the NEAREST rule above.  Nearest is a pure gather, so this is
+ *                   the reference's quantise-then-resize.  NEAREST is what Image.fromarray(u16).resize((512, 512)) does under the reference's pinned
+ *                   Pillow 10.0.1 (environment.yaml:227: modes with ';' default to NEAREST); Pillow 12 defaults to BICUBIC for "I;16".
+ *     out_f32       optional fp32 [P, h, w]: v, the combined map before quantising
+ *     out_of_range  optional int32 [P, ho] (overwritten): per label row, the gathered pixels with t outside [0, 65536) or NaN.  One wave owns a row and adds
+ *                   its ballots in order; the caller sums the rows.  No atomics.
+ * hi, ho <= 262140 (resize), batch / P <= 65535.
+ * ---------------------------------------------------------------------------------------- */
+#define ADA_PIL_NEAREST 0     /* Pillow's Image.NEAREST */
+#define ADA_PIL_BICUBIC 3     /* Pillow's Image.BICUBIC */
+#define ADA_LABEL_WRAP 0
+#define ADA_LABEL_CLIP 1
+int ada_pil_resize_u8_fwd(const uint8_t* src, int32_t batch, int32_t hi, int32_t wi, int32_t channels, int64_t row_pitch_bytes,
+                          int64_t image_stride_bytes, int32_t ho, int32_t wo, int32_t filter, const int32_t* bounds_x, const int32_t* kk_x,
+                          int32_t ksize_x, const int32_t* bounds_y, const int32_t* kk_y, int32_t ksize_y, uint8_t* tmp, int64_t tmp_bytes,
+                          uint8_t* out_u8, float* out_f32, uint8_t* out_mask, void* stream);
+int ada_label_combine_fwd(const float* whole, const float* occ, const uint8_t* whole_mask, const float* scale_shift, int32_t batch, int32_t h,
+                          int32_t w, int32_t ho, int32_t wo, int32_t overflow, uint16_t* out_u16, float* out_f32, int32_t* out_of_range,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Tiled inference for inputs larger than the network's native 518 x 518 (the reference squashes every
  * input to 518 x 518, infer.py:17,84).  ada_tile_blend_fwd merges the per-tile predictions:
  *   tiles     fp32 [B, T, tile_h, tile_w]; tile t covers rows origin_y[t].. and columns origin_x[t].. of the full map
