@@ -382,7 +382,16 @@ __global__ __launch_bounds__(256) void bilinear_tiled_kernel(BilinearArgs p, int
         const float fy = p.sy * (float)y, fx = p.sx * (float)x;
         const int y0 = (int)fy, x0 = (int)fx;
         const int y1 = y0 + (y0 < p.hi - 1 ? 1 : 0), x1 = x0 + (x0 < p.wi - 1 ? 1 : 0);
-        const float ly1 = fy - (float)y0, lx1 = fx - (float)x0;
+        // the weights come from the ROUNDED coordinate, as the tap index does, and as in the per-pixel kernel and in ATen: left to the compiler,
+        // fy - y0 was contracted with the product above into fma(sy, y, -y0), the fraction of the unrounded coordinate -- slightly negative where
+        // the product rounds up to an integer -- and the two kernels behind this entry point disagreed by up to 2^-24 * coordinate * (difference
+        // of the two taps), far beyond their rounding error (tests/test_gpu_resize_geometry.py).  Same instruction count: a v_sub for the v_fma.
+        float ly1, lx1;
+        {
+#pragma clang fp contract(off)
+            ly1 = fy - (float)y0;
+            lx1 = fx - (float)x0;
+        }
         const float ly0 = 1.0f - ly1, lx0 = 1.0f - lx1;
         const char* t0 = bl_smem + ((y0 - py0) * pw - px0) * 512 + g * 16;
         const char* t1 = bl_smem + ((y1 - py0) * pw - px0) * 512 + g * 16;
