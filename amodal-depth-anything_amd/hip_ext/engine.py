@@ -24,7 +24,6 @@ from collections import OrderedDict
 from typing import Dict, Optional
 
 import torch
-import torch.nn.functional as F
 
 from . import (A_CONV3, ACT_NONE, ACT_RELU, ACT_SIGMOID, EP_BIAS, EP_GAMMA, EP_GELU, EP_RELU_OP, EP_RESIDUAL,
                EP_SWIGLU, EP_TAIL, MAP_PAD, MAP_SHUFFLE, MAP_TOKEN, HipExtError)
@@ -41,7 +40,9 @@ from . import patchify as k_patchify
 from . import pos_embed_resize as k_pos_embed_resize
 from . import tapsum_resize as k_tapsum_resize
 from . import write_cls as k_write_cls
+from . import operands as O
 from .ladder import ladder_curve, ladder_decide, ladder_thresholds, next_start_rung, rung_counts  # noqa: F401  (ladder_curve: re-exported)
+from .operands import f8_weight_split  # noqa: F401  (re-exported)
 
 _probe = None   # list of (label, device counter) while DepthEngine.saturation_report runs, else None
 
@@ -100,34 +101,6 @@ OC1_COMMUTE = os.environ.get("ADA_OC1_COMMUTE", "1") != "0"     # operand-typed 
 _F8_ENV = os.environ.get("ADA_F8_CORR", "1")     # 1 | 0 | enc | head (A/B: only the encoder's split blocks / only the head's split groups)
 F8_CORR = _F8_ENV != "0"
 F8_ENC, F8_HEAD = _F8_ENV in ("1", "enc"), _F8_ENV in ("1", "head")
-F8_A_SCALES = 117 | (127 << 16)     # E8M0 bytes of the activation's two byte segments: lo8 = e5m2((x - x_hi) 2^10), hi8 = e5m2(x)
-
-
-def f8_weight_split(wm: torch.Tensor, op, taps: int = 1):
-    """[N, taps * K] fp32 (K a multiple of 128) -> ([N, taps * 2 K] operand-typed storage, f8_scales word): per tap [w_hi | w_hi8 | w_lo8] with
-    w_hi = round(w) in the operand type (K slots), then K bytes e4m3(w_hi 2^s_hi) and K bytes e4m3((w - w_hi) 2^s_lo), one power-of-two scale per
-    tensor and segment chosen so that the largest magnitude lands in [224, 448].  The contraction against an activation stored [hi | lo8 | hi8]
-    (split_seg = -K) evaluates x_hi w_hi + 2^-10 x_lo8 w_hi8 2^-s_hi + x_hi8 w_lo8 2^-s_lo (include/ada_hip.h, ada_igemm_args.f8_from)."""
-    n = wm.shape[0]
-    k = wm.shape[1] // taps
-    assert wm.shape[1] == taps * k and k % 128 == 0, (wm.shape, taps)
-    w = wm.reshape(n, taps, k).float()
-    hi = w.to(op)
-    lo = w - hi.float()
-
-    def enc(t):
-        m = float(t.abs().max())
-        sh = max(-100, min(100, int(math.floor(math.log2(448.0 / m))))) if m > 0 else 0
-        q = (t.float() * (2.0 ** sh)).clamp(-448.0, 448.0)
-        try:
-            b = q.to(torch.float8_e4m3fn).view(torch.uint8)
-        except (RuntimeError, TypeError):      # no device cast for the dtype on this backend
-            b = q.cpu().to(torch.float8_e4m3fn).view(torch.uint8).to(t.device)
-        return b, 127 - sh
-    hi8, sb_hi = enc(hi)
-    lo8, sb_lo = enc(lo)
-    packed = torch.cat([hi.contiguous().view(torch.uint8).reshape(n, taps, 2 * k), hi8, lo8], dim=2).reshape(n, taps * 4 * k)
-    return packed.contiguous().view(op), F8_A_SCALES | (sb_hi << 8) | (sb_lo << 24)
 
 
 def fused_tail_applies(half, halfp, hi, ho, split):
@@ -170,12 +143,9 @@ class PackedWeights:
         cfg = VIT[encoder]
         D = cfg["dim"]
         self.encoder, self.guided, self.amodal_head = encoder, guided, amodal_head
-        # split_head: contractions of the DPT head run in split precision -- activations are stored as [hi | lo] column segments by the
-        # producing kernel (split_seg), weights are packed [w_hi | w_hi | w_lo], and one fp16 GEMM over the three k segments (hi, lo, hi:
-        # the third re-reads the first, ada_igemm a_dup_seg) evaluates x_hi w_hi + x_lo w_hi + x_hi w_lo (~fp32 operand accuracy).  Used where the head's operand rounding
-        # is what limits parity: the unbounded-output models (raw ReLU / 'ssi' heads) and ViT-S.
-        # The choice is PER LAYER GROUP (HEAD_GROUPS): a contraction of a split group reads a [hi | lo] activation (its producer is
-        # told through split_seg) and [w_hi | w_hi | w_lo] weights; the others run at 1x the MACs.  True = every group.
+        # split_head: contractions of the DPT head run in split precision (~fp32 operand accuracy at 3x the MACs, 2x with fp8 correction terms), PER LAYER
+        # GROUP (HEAD_GROUPS; True = every group).  The forms of the weights and activations, and who decides them: DESIGN.md section 4.1.  Used where the
+        # head's operand rounding is what limits parity: the unbounded-output models (raw ReLU / 'ssi' heads) and ViT-S.
         if split_head is True:
             split_head = HEAD_GROUPS
         self.split = frozenset(g for name in (split_head or ()) for g in HEAD_ALIASES.get(name, (name,)))
@@ -186,13 +156,12 @@ class PackedWeights:
         # enc_split_blocks = K: the linear layers of the FIRST K transformer blocks run in split precision.  Operand rounding noise injected
         # early is amplified by every later block (oracle study, profiles/r04_e_raw_vitg_operand_noise_by_block.txt: blocks 0-9 of ViT-G carry
         # half of the encoder's share, blocks 30-39 a fiftieth), so for the unbounded-output ViT-G model, whose encoder alone reaches
-        # 0.7e-3 ... 1.05e-3 depending on the weight draw, the head's split precision is not enough.  qkv and fc1 / w12 read the LayerNorm
-        # output as [hi | lo] (full three-term product).  Round 6: so do proj and fc2 / w3 -- the attention kernel and the GELU / SwiGLU epilogues write
-        # the attention output and the MLP hidden of a split block in the split form too (rounds 4-5 walked the plain activation twice against
-        # [w_hi | w_lo]: the weight's rounding error went, the activation's stayed -- and that was what bounded the everything-split engine: raw ViT-G
-        # 6.2e-4 of output error from these two activations alone against 2.9e-4 from the attention core, oracle/study_rung3_floor.py).
+        # 0.7e-3 ... 1.05e-3 depending on the weight draw, the head's split precision is not enough.  All four linear layers of a split block take the
+        # full product: the attention kernel and the GELU / SwiGLU epilogues write their outputs in the split form too (rounds 4-5 walked the plain
+        # activation twice against [w_hi | w_lo]: the weight's rounding error went, the activation's stayed -- and that was what bounded the everything-split
+        # engine: raw ViT-G 6.2e-4 of output error from these two activations alone against 2.9e-4 from the attention core, oracle/study_rung3_floor.py).
         self.enc_split_blocks = max(0, min(int(enc_split_blocks), cfg["depth"]))
-        # ... with the two correction terms of qkv / fc1 / w12 on the fp8 matrix pipe where the build has it (fp16 operands, D a multiple of 128)
+        # ... with the two correction terms on the fp8 matrix pipe where the build has it (fp16 operands, D a multiple of 128)
         # f8: which of the two users take it -- "both" | "enc" | "head" | "none" (the caller's precision policy, DA2/dpt.py::_f8_policy)
         if f8 not in ("both", "enc", "head", "none"):
             raise HipExtError(f"PackedWeights: f8={f8!r} (both | enc | head | none)")
@@ -203,38 +172,48 @@ class PackedWeights:
         # the ladder's second rung, which are packed later from the same state_dict
         self.tap_f8 = (self.f8_head if tap_f8 is None else (bool(tap_f8) and F8_HEAD and op == torch.float16)) and D % 128 == 0
         self.dim, self.depth, self.heads, self.ffn = D, cfg["depth"], cfg["heads"], cfg["ffn"]
+        self.op = op
+        # reader -> the activation form it reads (act_form).  The taps are split when the projects read them so -- or the engine keeps them for the second rung
+        self.reads = {"tap": (O.A_HILO8 if self.tap_f8 else O.A_HILO) if (self.tap_split or "proj" in self.split) else O.A_PLAIN}
 
         def f32(name):
             return sd[name].detach().to(torch.float32).contiguous()
 
-        def lin(w):  # [N, K] -> operand type, K padded to 64
-            w = w.reshape(w.shape[0], -1)
-            k = w.shape[1]
-            if k % 64:
-                w = F.pad(w, (0, _r64(k) - k))
-            return w.to(op).contiguous()
-
-        def conv3(w):  # [Co, Ci, 3, 3] -> [Co, 9 * Cip], tap-major
-            co, ci = w.shape[:2]
-            w = w.permute(0, 2, 3, 1)
-            if ci % 64:
-                w = F.pad(w, (0, _r64(ci) - ci))
-            return w.reshape(co, -1).to(op).contiguous()
-
-        def convT(w, b, s):  # [Ci, Co, s, s] -> [s*s*Co, Cip], bias expanded to [s*s*Co]
-            ci, co = w.shape[:2]
-            wt = w.permute(2, 3, 1, 0).reshape(s * s * co, ci)
-            return lin(wt), b.repeat(s * s).contiguous()
-
-        p = "pretrained."
         self.blocks = []
         self.guide_channels = 0
         if not head_only:
-            self._pack_encoder(sd, f32, lin, op, D, guided)
-        self._pack_head(sd, f32, lin, conv3, op, D, amodal_head)
+            self._pack_encoder(sd, f32, D, guided)
+        self._pack_head(sd, f32, D, amodal_head)
+        # head groups whose producers write [hi | lo8 | hi8]
+        self.f8_groups = {g for g in HEAD_GROUPS if self.reads.get(g) is O.A_HILO8}
+        for p in self.proj_w + (self.ro_wx + self.ro_wc if self.readout else []):     # the one pair whose two sides are chosen apart (tap_f8): refused here, not at launch
+            O.walk(p, self.reads["tap"], self.reads["tap"].width(D))
 
-    def _pack_encoder(self, sd, f32, lin, op, D, guided):
-        p = "pretrained."
+    def _form(self, group, seg, weight_only=False):
+        """THE choice of a head contraction's weight form.  A split group takes the full product, its two correction terms on the fp8
+        pipe where the policy (f8, f8_only) allows it and the padded channel count is a multiple of 128; ``weight_only``: [w_hi | w_lo] outside a split group."""
+        if group not in self.split:
+            return O.W_SPLIT2 if weight_only else O.W_PLAIN
+        f8 = self.f8_head and (self.f8_only is None or group in self.f8_only) and seg % 128 == 0
+        return O.W_F8 if f8 else O.W_SPLIT3
+
+    def _pack(self, w, group, taps=1, weight_only=False) -> O.Packed:
+        """[N, taps, K] (any trailing shape) fp32 weights of a contraction of ``group``, in the group's form; what its producers must write is recorded."""
+        w = w.reshape(w.shape[0], -1)
+        p = O.pack(w, self._form(group, _r64(w.shape[1] // taps), weight_only), self.op, taps)
+        if self.reads.setdefault(group, O.reads(p.form)) is not O.reads(p.form):
+            raise HipExtError(f"head group {group!r}: {p.form} weights against the {self.reads[group].name} operand of the group's other contractions")
+        return p
+
+    def act_form(self, reader) -> O.ActForm:
+        """The form the producers of a contraction's A operand must write and its buffer holds.  ``reader``: a head group, "tap" (the four taps and the class
+        tokens), "sp<i>" (the merged sub-pixel convolution of level i), or the index of an encoder block (its LayerNorm / attention / MLP-hidden rows)."""
+        if isinstance(reader, int):
+            return O.reads(self.blocks[reader]["qkv_w"].form)
+        return self.reads.get(reader, O.A_PLAIN)
+
+    def _pack_encoder(self, sd, f32, D, guided):
+        p, op = "pretrained.", self.op
         w_rgb = f32(p + "patch_embed.proj.weight").reshape(D, -1)
         b_pe = f32(p + "patch_embed.proj.bias")
         if guided:
@@ -243,23 +222,14 @@ class PackedWeights:
             w_rgb = torch.cat([w_rgb, w_g.reshape(D, -1)], dim=1)
             b_pe = b_pe + f32(p + "patch_embed_guidance.proj.bias")
         # split-precision patch embedding: the image is the one operand whose fp16 rounding error (2.5e-4 relative) is
-        # injected into every token, so it is carried as hi + lo halves and the weights likewise; one GEMM over
-        # K = 3 * 1024 computes x_hi w_hi + x_lo w_hi + x_hi w_lo (0.6 % of the model's MACs instead of 0.2 %).
-        k_real = w_rgb.shape[1]
-        seg = _r64(k_real)
-        w_pad = F.pad(w_rgb, (0, seg - k_real))
-        w_hi = w_pad.to(op)
-        w_lo = (w_pad - w_hi.float()).to(op)
-        self.pe_w = torch.cat([w_hi, w_hi, w_lo], dim=1).contiguous()
+        # injected into every token, so it is carried as hi + lo halves and the weights likewise (0.6 % of the model's MACs instead of 0.2 %)
+        self.pe_w = O.pack(w_rgb, O.W_SPLIT3, op)
         self.pe_b = b_pe.contiguous()
-        self.pe_k = self.pe_w.shape[1]      # K of the embedding GEMM: three segments (hi, lo, hi) of pe_seg
-        self.pe_seg = seg
-        self.pe_k_alg = k_real
+        self.pe_seg = self.pe_w.seg
         self.cls = f32(p + "cls_token").reshape(D)
         self.pos_native = f32(p + "pos_embed")  # [1, 1 + 37*37, D]
         self._pos_cache: Dict[tuple, torch.Tensor] = {}
 
-        self.blocks = []
         for i in range(self.depth):
             b = f"{p}blocks.{i}."
             qw, qb = f32(b + "attn.qkv.weight").clone(), f32(b + "attn.qkv.bias").clone()
@@ -267,29 +237,19 @@ class PackedWeights:
             # kernel runs its softmax in base 2 (exp2 is the native transcendental), softmax_e(s) == softmax_2(s * log2 e)
             qw[:D] *= Q_PRESCALE
             qb[:D] *= Q_PRESCALE
-            esplit = i < self.enc_split_blocks
+            form = O.W_PLAIN if i >= self.enc_split_blocks else O.W_F8 if self.enc_f8 else O.W_SPLIT3
 
-            def lin3(wm):   # [N, K] -> [w_hi | w_hi | w_lo] (against a [hi | lo] activation, a_dup_seg) for the split blocks
-                if not esplit:
-                    return lin(wm), 0
-                if self.enc_f8:  # ... or [w_hi | w_hi8 | w_lo8] against [hi | lo8 | hi8] (f8_from): the two correction terms on the fp8 pipe
-                    return f8_weight_split(wm, op)
-                hi_ = wm.to(op)
-                return torch.cat([hi_, hi_, (wm - hi_.float()).to(op)], dim=1).contiguous(), 0
+            def lin(name):
+                return O.pack(name if torch.is_tensor(name) else f32(b + name), form, op)
 
-            qkv_w, qkv_f8 = lin3(qw)
-            proj_w, proj_f8 = lin3(f32(b + "attn.proj.weight"))
             blk = dict(
-                ln1_w=f32(b + "norm1.weight"), ln1_b=f32(b + "norm1.bias"), esplit=esplit,
-                qkv_w=qkv_w, qkv_f8=qkv_f8, qkv_b=qb,
-                proj_w=proj_w, proj_f8=proj_f8, proj_b=f32(b + "attn.proj.bias"), ls1=f32(b + "ls1.gamma"),
+                ln1_w=f32(b + "norm1.weight"), ln1_b=f32(b + "norm1.bias"), qkv_w=lin(qw), qkv_b=qb,
+                proj_w=lin("attn.proj.weight"), proj_b=f32(b + "attn.proj.bias"), ls1=f32(b + "ls1.gamma"),
                 ln2_w=f32(b + "norm2.weight"), ln2_b=f32(b + "norm2.bias"), ls2=f32(b + "ls2.gamma"),
             )
             if self.ffn == "mlp":
-                fc1_w, fc1_f8 = lin3(f32(b + "mlp.fc1.weight"))
-                fc2_w, fc2_f8 = lin3(f32(b + "mlp.fc2.weight"))
-                blk.update(fc1_w=fc1_w, fc1_f8=fc1_f8, fc1_b=f32(b + "mlp.fc1.bias"), fc2_w=fc2_w, fc2_f8=fc2_f8, fc2_b=f32(b + "mlp.fc2.bias"))
-                blk["hidden"] = blk["fc1_w"].shape[0]
+                blk.update(fc1_w=lin("mlp.fc1.weight"), fc1_b=f32(b + "mlp.fc1.bias"), fc2_w=lin("mlp.fc2.weight"), fc2_b=f32(b + "mlp.fc2.bias"))
+                blk["hidden"] = blk["fc1_w"].t.shape[0]
             else:
                 w12, b12 = f32(b + "mlp.w12.weight"), f32(b + "mlp.w12.bias")
                 hid = w12.shape[0] // 2
@@ -297,61 +257,17 @@ class PackedWeights:
                 # interleave x1 / x2 rows in groups of 32 so one wave's two MFMA column tiles hold the gate pair
                 idx = torch.arange(hid, device=w12.device).reshape(-1, 32)
                 order = torch.stack([idx, idx + hid], dim=1).reshape(-1)
-                w12_w, w12_f8 = lin3(w12[order])
-                w3_w, w3_f8 = lin3(f32(b + "mlp.w3.weight"))
-                blk.update(w12_w=w12_w, w12_f8=w12_f8, w12_b=b12[order].contiguous(), w3_w=w3_w, w3_f8=w3_f8, w3_b=f32(b + "mlp.w3.bias"))
+                blk.update(w12_w=lin(w12[order]), w12_b=b12[order].contiguous(), w3_w=lin("mlp.w3.weight"), w3_b=f32(b + "mlp.w3.bias"))
                 blk["hidden"] = hid
             self.blocks.append(blk)
         self.norm_w, self.norm_b = f32(p + "norm.weight"), f32(p + "norm.bias")
 
-    def _pack_head(self, sd, f32, lin, conv3, op, D, amodal_head):
-        lin1, conv3_1 = lin, conv3
+    def _pack_head(self, sd, f32, D, amodal_head):
+        def conv3(w, group):  # [Co, Ci, 3, 3] -> tap-major
+            return self._pack(w.permute(0, 2, 3, 1), group, taps=9)
 
-        def triple(w2d):   # [..., K] fp32, K already padded to a multiple of 64
-            hi = w2d.to(op)
-            lo = (w2d - hi.float()).to(op)
-            return torch.cat([hi, hi, lo], dim=-1)
-
-        # Groups whose contractions take their two correction terms on the fp8 pipe (module comment at F8_CORR): the weights are [w_hi | w_hi8 | w_lo8]
-        # per tap, the activation [hi | lo8 | hi8] -- the group's PRODUCERS are told through a negative split_seg (_head: S()).  Needs the operand's
-        # channel count (padded) to be a multiple of 128; a group of another width keeps the three fp16 terms.
-        self.f8_groups = set()
-        f8_ok = self.f8_head
-
-        def f8_pack(w2d, group, taps):
-            t, word = f8_weight_split(w2d, op, taps=taps)
-            t.f8_scales = word          # read by DepthEngine._kdup: the packed shape alone does not tell this form from a plain operand
-            self.f8_groups.add(group)
-            return t
-
-        def lin(w, group):  # noqa: F811
-            if group not in self.split:
-                return lin1(w)
-            w = w.reshape(w.shape[0], -1)
-            k = w.shape[1]
-            if k % 64:
-                w = F.pad(w, (0, _r64(k) - k))
-            if f8_ok and (self.f8_only is None or group in self.f8_only) and w.shape[1] % 128 == 0:
-                return f8_pack(w, group, 1)
-            assert group not in self.f8_groups, group
-            return triple(w).contiguous()
-
-        def conv3(w, group):  # noqa: F811  [Co, Ci, 3, 3] -> [Co, 9 * 3 * Cip]: per tap [hi | hi | lo]
-            if group not in self.split:
-                return conv3_1(w)
-            co, ci = w.shape[:2]
-            w = w.permute(0, 2, 3, 1)
-            if ci % 64:
-                w = F.pad(w, (0, _r64(ci) - ci))
-            if f8_ok and (self.f8_only is None or group in self.f8_only) and w.shape[-1] % 128 == 0:
-                return f8_pack(w.reshape(co, -1), group, 9)
-            assert group not in self.f8_groups, group
-            return triple(w).reshape(co, -1).contiguous()
-
-        def convT(w, b, s_, group):  # noqa: F811  [Ci, Co, s, s] -> [s*s*Co, Cip], bias expanded to [s*s*Co]
-            ci, co = w.shape[:2]
-            wt = w.permute(2, 3, 1, 0).reshape(s_ * s_ * co, ci)
-            return lin(wt, group), b.repeat(s_ * s_).contiguous()
+        def convT(w, b, s_, group):  # [Ci, Co, s, s] -> [s*s*Co, Ci], bias expanded to [s*s*Co]
+            return self._pack(w.permute(2, 3, 1, 0).reshape(s_ * s_ * w.shape[1], w.shape[0]), group), b.repeat(s_ * s_).contiguous()
 
         h = "depth_head."
         # use_clstoken read-out (reference DA2/dpt.py:110-117,164-167): Linear(2D -> D) on [patch token | class token] + GELU.  The class
@@ -362,47 +278,38 @@ class PackedWeights:
             self.ro_wx, self.ro_wc, self.ro_b = [], [], []
             for i in range(4):
                 wr = f32(f"{h}readout_projects.{i}.0.weight")
-                self.ro_wx.append(lin(wr[:, :D], "proj"))
-                self.ro_wc.append(lin(wr[:, D:], "proj"))
+                self.ro_wx.append(self._pack(wr[:, :D], "proj"))
+                self.ro_wc.append(self._pack(wr[:, D:], "proj"))
                 self.ro_b.append(f32(f"{h}readout_projects.{i}.0.bias"))
         self.oc = [sd[f"{h}projects.{i}.weight"].shape[0] for i in range(4)]
         self.features = sd[h + "scratch.layer1_rn.weight"].shape[0]
-        def proj_lin(w):   # "projw": [w_hi | w_lo] against the plain tap (HEAD_GROUPS comment); "proj" (full split) takes precedence
-            w2 = w.reshape(w.shape[0], -1)
-            if "projw" in self.split and "proj" not in self.split and w2.shape[1] % 64 == 0:
-                hi = w2.to(op)
-                return torch.cat([hi, (w2 - hi.float()).to(op)], dim=1).contiguous()
-            return lin(w, "proj")
-        self.proj_w = [proj_lin(f32(f"{h}projects.{i}.weight")) for i in range(4)]
+        # "projw": weight-only split of the four projects (HEAD_GROUPS comment); "proj" (full split) takes precedence
+        self.proj_w = [self._pack(f32(f"{h}projects.{i}.weight"), "proj", weight_only="projw" in self.split) for i in range(4)]
         self.proj_b = [f32(f"{h}projects.{i}.bias") for i in range(4)]
         self.rs0_w, self.rs0_b = convT(f32(h + "resize_layers.0.weight"), f32(h + "resize_layers.0.bias"), 4, "rs0")
         self.rs1_w, self.rs1_b = convT(f32(h + "resize_layers.1.weight"), f32(h + "resize_layers.1.bias"), 2, "rs1")
         self.rs3_w, self.rs3_b = conv3(f32(h + "resize_layers.3.weight"), "rs3"), f32(h + "resize_layers.3.bias")
-        # level -> merged sub-pixel convolution (single-precision levels only): resize_layers[i] + input_projection[i][0] in the amodal head,
+        # level -> merged sub-pixel convolution: resize_layers[i] + input_projection[i][0] in the amodal head,
         # resize_layers[i] + scratch.layer{i+1}_rn (no bias, util/blocks.py:20-24) in the raw head
         self.sp = {}
         if SUBPIXEL:
             from .functional import subpixel_merge
             nxt = "ip" if amodal_head else "rn"
             for i, s_ in ((0, 4), (1, 2)):
-                # (round 6) a level whose transposed conv AND the 3x3 conv behind it are split groups with fp8 correction terms is merged too: the merged weights are
-                # packed [w_hi | w_hi8 | w_lo8] per tap and `projects[i]` writes the patch-grid tensor [hi | lo8 | hi8] (needs a channel count that is a multiple of 128)
-                both = f"rs{i}" in self.split and f"{nxt}{i}" in self.split
-                if (f"rs{i}" in self.split or f"{nxt}{i}" in self.split) and not (
-                        SUBPIXEL_SPLIT and both and f8_ok and _r64(sd[f"{h}projects.{i}.weight"].shape[0]) % 128 == 0
-                        and (self.f8_only is None or {f"rs{i}", f"{nxt}{i}"} <= self.f8_only)):
+                # single-precision levels -- and (round 6) a level whose transposed conv AND the 3x3 conv behind it are split groups with fp8 correction terms: the
+                # merged weights take the 3x3 conv's form and `projects[i]` writes the patch-grid tensor [hi | lo8 | hi8]
+                groups = {f"rs{i}", f"{nxt}{i}"}
+                if groups & self.split and not (SUBPIXEL_SPLIT and groups <= self.split
+                                                and all(self._form(g, _r64(self.oc[i])) == O.W_F8 for g in groups)):
                     continue
                 if amodal_head:
                     w3_, b3_ = f32(f"{h}input_projection.{i}.0.weight"), f32(f"{h}input_projection.{i}.0.bias")
                 else:
                     w3_, b3_ = f32(f"{h}scratch.layer{i + 1}_rn.weight"), None
                 wm, bias, tapb, masks = subpixel_merge(f32(f"{h}resize_layers.{i}.weight"), f32(f"{h}resize_layers.{i}.bias"), w3_, b3_, s_)
-                ci = wm.shape[2]
-                if ci % 64:
-                    wm = F.pad(wm, (0, _r64(ci) - ci))
-                wq = f8_pack(wm.reshape(wm.shape[0], -1), f"{nxt}{i}", 9) if both else wm.reshape(wm.shape[0], -1).to(op).contiguous()
-                self.sp[i] = dict(s=s_, w=wq, b=bias, tapb=tapb, masks=masks, split=both,
+                self.sp[i] = dict(s=s_, w=self._pack(wm, f"{nxt}{i}", taps=9), b=bias, tapb=tapb, masks=masks,
                                   taps_per_col=sum(bin(m).count("1") for m in masks) / float(s_ * s_))
+                self.reads[f"sp{i}"] = O.reads(self.sp[i]["w"].form)
         if amodal_head:
             self.ip_w = [conv3(f32(f"{h}input_projection.{i}.0.weight"), f"ip{i}") for i in range(4)]
             self.ip_b = [f32(f"{h}input_projection.{i}.0.bias") for i in range(4)]
@@ -413,7 +320,7 @@ class PackedWeights:
         self.fuse = []
         for k in range(1, 5):
             r = f"{s}refinenet{k}."
-            d = dict(out_w=lin(f32(r + "out_conv.weight"), f"out{k - 1}"), out_b=f32(r + "out_conv.bias"))
+            d = dict(out_w=self._pack(f32(r + "out_conv.weight"), f"out{k - 1}"), out_b=f32(r + "out_conv.bias"))
             for u in (1, 2):
                 for c in (1, 2):
                     w, b = f32(f"{r}resConfUnit{u}.conv{c}.weight"), f32(f"{r}resConfUnit{u}.conv{c}.bias")
@@ -426,29 +333,24 @@ class PackedWeights:
             self.fuse.append(d)  # index k-1
         self.oc1_w, self.oc1_b = conv3(f32(s + "output_conv1.weight"), "oc1"), f32(s + "output_conv1.bias")
         self.oc1c = None     # output_conv1 composed with refinenet1.out_conv, one 1x1 per tap: [9 * half, Fp] (+ the bias each tap map carries)
-        half_ = self.features // 2
+        half_, Fp = self.features // 2, _r64(self.features)
         # (round 6) ... ALSO when "oc1" / "out0" are split groups with fp8 correction terms: the tap-map GEMM then reads u[0] as [hi | lo8 | hi8] against the composed
-        # matrix packed [w_hi | w_hi8 | w_lo8]; the nine tap maps stay operand-typed.  The ladder's second rung (-2 ms of its 27) and the raw ViT-B / ViT-L heads.
-        split_commute = (OC1_COMMUTE_SPLIT and "oc1" in self.split and "out0" in self.split and f8_ok and self.features % 128 == 0
-                         and (self.f8_only is None or {"oc1", "out0"} <= self.f8_only))
-        if OC1_COMMUTE and (split_commute or ("oc1" not in self.split and "out0" not in self.split)) and half_ in (32, 64, 128):
+        # matrix in the fp8 form; the nine tap maps stay operand-typed.  The ladder's second rung (-2 ms of its 27) and the raw ViT-B / ViT-L heads.
+        groups = {"oc1", "out0"}
+        split_commute = OC1_COMMUTE_SPLIT and groups <= self.split and all(self._form(g, Fp) == O.W_F8 for g in groups) and self.features % 128 == 0
+        if OC1_COMMUTE and (split_commute or not groups & self.split) and half_ in (32, 64, 128):
             from .functional import compose_f32
             w1 = f32(s + "output_conv1.weight")                                  # [half, F, 3, 3]
             wo_ = f32(s + "refinenet1.out_conv.weight").reshape(self.features, self.features)   # [F(cm), F(ci)]
             bo_ = f32(s + "refinenet1.out_conv.bias")
             wt_ = w1.permute(2, 3, 0, 1).reshape(9 * half_, self.features)       # rows (tap, co), columns cm
-            # [w_hi | w_lo] (ada_igemm a_wrap): rounding the COMPOSED matrix to the operand type once is not harmless -- its error acts on the
+            # weight-only split where the groups are single-precision: rounding the COMPOSED matrix to the operand type once is not harmless -- its error acts on the
             # activation's large common-mode part coherently over all taps and positions and survives the resizes and convolutions behind it
             # (oracle study: 5.3e-4 at the output of ViT-B from this rounding alone, against 1.0e-4 / 0.9e-4 for the two factors rounded
             # separately; profiles/r04_g_output_conv1_commute.txt).  K = 2 * 256 on a GEMM that is bound by its 1.6 GB of output anyway.
             wc_ = compose_f32(wt_, wo_.t())       # the library's own GEMM in split precision (functional.compose_f32); W_t b_out is a reduction
-            wc_hi = wc_.to(op)
             tap_b = (wt_.double() * bo_.double()[None, :]).sum(1).float().contiguous()
-            if split_commute:
-                wq, word = f8_weight_split(wc_, op)
-                self.oc1c = dict(w=wq, f8=word, b=tap_b)
-            else:
-                self.oc1c = dict(w=torch.cat([wc_hi, (wc_ - wc_hi.float()).to(op)], dim=1).contiguous(), b=tap_b)
+            self.oc1c = dict(w=self._pack(wc_, "out0", weight_only=True), b=tap_b)
         self.oc2_w, self.oc2_b = conv3(f32(s + "output_conv2.0.weight"), "oc2"), f32(s + "output_conv2.0.bias")
         self.tail_w = f32(s + "output_conv2.2.weight").reshape(-1).contiguous()
         self.tail_b = float(f32(s + "output_conv2.2.bias").reshape(-1)[0].item())
@@ -476,6 +378,15 @@ class PackedWeights:
 
 
 class Workspace:
+    @staticmethod
+    def widths(pw_: PackedWeights) -> Dict[str, int]:
+        """reader (PackedWeights.act_form) -> columns of the operand-typed buffer its contractions read: the form its producers write over the reader's segment."""
+        ocp, Fp = [_r64(c) for c in pw_.oc], _r64(pw_.features)
+        seg = {"tap": pw_.dim, "oc1": Fp, "oc2": _r64(pw_.features // 2)}
+        for i in range(4):
+            seg.update({f"rs{i}": ocp[i], f"ip{i}": ocp[i], f"rn{i}": ocp[i], f"sp{i}": ocp[i], f"rcu{i}": Fp, f"out{i}": Fp})
+        return {g: pw_.act_form(g).width(s) for g, s in seg.items()}
+
     def __init__(self, pw_: PackedWeights, B: int, H: int, W: int, device, head_only: bool = False):
         """head_only: the buffers of the DPT head and the four taps only (the precision ladder's second rung re-runs the head from the taps)."""
         op = operand_dtype()
@@ -488,27 +399,22 @@ class Workspace:
         T, P = B * N, B * Np
         Fch = pw_.features
         Fp = _r64(Fch)
-        def mm(group):     # an op-typed head tensor holds [hi | lo] segments iff the contraction that READS it is in a split group
-            return 2 if group in pw_.split else 1
-        # the taps are [hi | lo] when the projects read them in split precision -- or when the engine keeps them so for the ladder's second rung
-        m = 2 if (pw_.tap_split or "proj" in pw_.split) else 1
-        self.tap_seg = (-D if pw_.tap_f8 else D) if m == 2 else 0     # < 0: the [hi | lo8 | hi8] form (ada_igemm_args.f8_from)
+        cols = self.widths(pw_)     # an op-typed head tensor is as wide as the form the contraction that READS it needs
         first = "ip" if pw_.amodal_head else "rn"     # the contraction family that reads the reassembled maps L[i]
 
         def z(*shape, dtype=op):
             return torch.zeros(*shape, dtype=dtype, device=device)
 
         if not head_only:
-            self.a_pe = z(P, 2 * pw_.pe_seg)     # split-precision patches: [hi | lo]
+            self.a_pe = z(P, O.A_HILO.width(pw_.pe_seg))     # split-precision patches
             self.x = z(T, D, dtype=torch.float32)
-            # LayerNorm output ([hi | lo] column segments for the split-precision blocks: PackedWeights.enc_split_blocks)
-            self.y = z(T, 2 * D if pw_.enc_split_blocks > 0 else D)
+            # LayerNorm output, attention output, MLP hidden: one buffer each for every block, in the form of block 0 (split if any block is: enc_split_blocks)
+            enc = pw_.act_form(0)
+            self.y = z(T, enc.width(D))
             self.qkv = z(T, 3 * D)
-            wide = 2 if pw_.enc_split_blocks > 0 else 1       # attention output / MLP hidden: [hi | lo] / [hi | lo8 | hi8] rows in the split blocks
-            self.o = z(T, wide * D)
-            hidden = pw_.blocks[0]["hidden"]
-            self.hd = z(T, wide * hidden)
-        self.taps = [z(P, m * D) for _ in range(4)]
+            self.o = z(T, enc.width(D))
+            self.hd = z(T, enc.width(pw_.blocks[0]["hidden"]))
+        self.taps = [z(P, cols["tap"]) for _ in range(4)]
         # the precision ladder's per-image statistics, one buffer (one host read): stat_sums = (sum s, sum s (1 - s)) of the depth map in chunks
         # (ada_depth_stats_fwd), stat_div = (sum of column variances, sum of column mean squares) of the last tap in 64-column chunks (ada_token_diversity_fwd)
         # ... and stat_in = the same pair over the PATCHIFIED INPUT (a_pe: one row per patch, pixels + guide channels): exactly zero variance when every patch of the
@@ -520,9 +426,9 @@ class Workspace:
         self.stat_div = self.stat_buf[B * STAT_CHUNKS * 2:B * (STAT_CHUNKS + G) * 2].view(B, G, 2)
         self.stat_in = self.stat_buf[B * (STAT_CHUNKS + G) * 2:].view(B, Gi, 2) if Gi else None
         if pw_.readout:
-            self.cls_op = [z(B, m * D) for _ in range(4)]                          # final-LayerNorm'd class tokens, operand-typed
+            self.cls_op = [z(B, cols["tap"]) for _ in range(4)]                          # final-LayerNorm'd class tokens, operand-typed
             self.cls_bias = [z(B, D, dtype=torch.float32) for _ in range(4)]       # W_cls cls + b per image
-            self.taps_ro = [z(P, m * D) for _ in range(4)]                         # read-out tokens (inputs of `projects`)
+            self.taps_ro = [z(P, cols["tap"]) for _ in range(4)]                         # read-out tokens (inputs of `projects`)
         # head grids
         self.grid = [(4 * ph, 4 * pw), (2 * ph, 2 * pw), (ph, pw), ((ph - 1) // 2 + 1, (pw - 1) // 2 + 1)]
         oc = pw_.oc
@@ -530,19 +436,19 @@ class Workspace:
         self.ocp, self.Fp = ocp, Fp
         # levels whose resize + first 3x3 conv run as one sub-pixel convolution: `projects[i]` writes a zero-bordered patch-grid tensor tp[i]
         # (the conv's A operand); t<i> and the up-sampled map L[i] do not exist
-        self.tp = {i: z(B, ph + 2, pw + 2, (2 if pw_.sp[i].get("split") else 1) * ocp[i]) for i in pw_.sp}
-        self.t0 = None if 0 in pw_.sp else z(P, mm("rs0") * ocp[0])
-        self.t1 = None if 1 in pw_.sp else z(P, mm("rs1") * ocp[1])
-        self.pre3 = z(B, ph + 2, pw + 2, mm("rs3") * ocp[3])
-        self.L = [None if i in pw_.sp else z(B, g[0] + 2, g[1] + 2, mm(f"{first}{i}") * ocp[i]) for i, g in enumerate(self.grid)]
+        self.tp = {i: z(B, ph + 2, pw + 2, cols[f"sp{i}"]) for i in pw_.sp}
+        self.t0 = None if 0 in pw_.sp else z(P, cols["rs0"])
+        self.t1 = None if 1 in pw_.sp else z(P, cols["rs1"])
+        self.pre3 = z(B, ph + 2, pw + 2, cols["rs3"])
+        self.L = [None if i in pw_.sp else z(B, g[0] + 2, g[1] + 2, cols[f"{first}{i}"]) for i, g in enumerate(self.grid)]
         if pw_.amodal_head:
             self.ipf = [z(B * g[0] * g[1], oc[i], dtype=torch.float32) for i, g in enumerate(self.grid)]
-            self.L2 = [z(B, g[0] + 2, g[1] + 2, mm(f"rn{i}") * ocp[i]) for i, g in enumerate(self.grid)]
+            self.L2 = [z(B, g[0] + 2, g[1] + 2, cols[f"rn{i}"]) for i, g in enumerate(self.grid)]
         self.rnx = [z(B * g[0] * g[1], Fch, dtype=torch.float32) for g in self.grid]
         # raw head: [patch, s*s*features] fp32 output of a merged resize + layer_rn convolution, re-laid out into rnx / rnr by one pass
         self.spf = {} if pw_.amodal_head else {i: z(B * self.grid[i][0] * self.grid[i][1], Fch, dtype=torch.float32) for i in pw_.sp}
-        self.rnr = [z(B, g[0] + 2, g[1] + 2, mm(f"rcu{i}") * Fp) for i, g in enumerate(self.grid)]
-        self.tmpa = [z(B, g[0] + 2, g[1] + 2, mm(f"rcu{i}") * Fp) for i, g in enumerate(self.grid)]
+        self.rnr = [z(B, g[0] + 2, g[1] + 2, cols[f"rcu{i}"]) for i, g in enumerate(self.grid)]
+        self.tmpa = [z(B, g[0] + 2, g[1] + 2, cols[f"rcu{i}"]) for i, g in enumerate(self.grid)]
         # fp32 side buffers whose lifetimes do not overlap share storage (plain row buffers only: the zero-bordered operand tensors keep their own,
         # their borders are written once).  Launch order of _head: ip conv -> LN (ipf dead) ... rn convs ... per level i = 3..0:
         # RCU2(i) [reads s[i]] -> out_conv [writes zf[i]] -> RCU1(i-1) [reads rnx[i-1], writes r[i-1]] -> resize [reads zf[i], r[i-1], writes s[i-1]];
@@ -558,12 +464,12 @@ class Workspace:
             else:
                 self.r.append(z(rows[i], Fch, dtype=torch.float32))
             self.s.append(z(rows[i], Fch, dtype=torch.float32))
-        self.sr = [z(B, g[0] + 2, g[1] + 2, mm(f"rcu{i}") * Fp) for i, g in enumerate(self.grid)]
-        self.u = [z(B * g[0] * g[1], mm(f"out{i}") * Fp) for i, g in enumerate(self.grid)]
+        self.sr = [z(B, g[0] + 2, g[1] + 2, cols[f"rcu{i}"]) for i, g in enumerate(self.grid)]
+        self.u = [z(B * g[0] * g[1], cols[f"out{i}"]) for i, g in enumerate(self.grid)]
         self.zf = self.rnx
         g0 = self.grid[0]
         self.g296 = (2 * g0[0], 2 * g0[1])
-        self.p1 = None if pw_.oc1c is not None else z(B, self.g296[0] + 2, self.g296[1] + 2, mm("oc1") * Fp)
+        self.p1 = None if pw_.oc1c is not None else z(B, self.g296[0] + 2, self.g296[1] + 2, cols["oc1"])
         # the nine tap maps of output_conv1 on the level-0 grid
         self.tmaps = z(rows[0], 9 * (Fch // 2)) if pw_.oc1c is not None else None
         half = Fch // 2
@@ -572,7 +478,7 @@ class Workspace:
         # fused tail (ada_dpt_tail_fwd): resize + output_conv2 in one kernel, the up-sampled map is never materialised.  Needs the
         # single-precision head and a channel count that is already a multiple of 64 (ViT-B / ViT-L heads)
         self.fused_tail = FUSED_TAIL and fused_tail_applies(half, self.halfp, self.g296[0], H, pw_.split)
-        self.fin = None if self.fused_tail else z(B, H + 2, W + 2, mm("oc2") * self.halfp)
+        self.fin = None if self.fused_tail else z(B, H + 2, W + 2, cols["oc2"])
 
 
 # Head branches on side streams (round 6): the four reassemble -> input_projection -> layerN_rn chains (DA2/dpt.py:161-187) and the
@@ -712,44 +618,15 @@ class DepthEngine:
 
     # ---- small helpers over igemm ---------------------------------------------------------
     @staticmethod
-    def _kdup(a_width: int, w: torch.Tensor, taps: int = 1, a_seg: int = 0) -> dict:
-        """K / lda / a_dup_seg of a contraction whose A rows are ``a_width`` wide and whose packed weights are ``w`` [N, K]: either a plain
-        operand (K == taps * a_width) or a split one -- [hi | lo] activations against [w_hi | w_hi | w_lo] weights, 2 K == 3 taps a_width,
-        the third k segment re-reading the first (ada_igemm a_dup_seg)."""
-        K = int(w.shape[1])
-        word = getattr(w, "f8_scales", 0)
-        if word:      # [w_hi | w_hi8 | w_lo8] per tap against [hi | lo8 | hi8] rows: a straight walk whose second half goes to the fp8 pipe (ada_igemm_args.f8_from)
-            seg = abs(a_seg) or a_width // 2
-            if K != 2 * taps * seg or (a_seg > 0):
-                raise HipExtError(f"fp8-form weights with K={K} do not fit an operand with segments of {a_seg or seg} ({taps} tap(s))")
-            return dict(K=K, lda=a_width, f8_from=seg, f8_mid=seg + seg // 2, f8_scales=word)
-        if a_seg < 0:
-            if K == 3 * -a_seg:
-                raise HipExtError("three-term fp16 weights against a [hi | lo8 | hi8] operand")
-            a_seg = -a_seg
-        if a_seg:     # the A rows ARE [hi | lo] segments of width a_seg (a tap of an engine that keeps them so): the weights decide what is walked
-            if K == 3 * a_seg:
-                return dict(K=K, lda=a_width, a_dup_seg=a_seg)
-            if K == a_seg:                       # single-precision contraction: the hi half only
-                return dict(K=K, lda=a_width, a_dup_seg=0)
-            if K == 2 * a_seg:                   # [w_hi | w_lo] against the hi half walked twice
-                return dict(K=K, lda=a_width, a_dup_seg=0, a_wrap=a_seg)
-            raise HipExtError(f"packed weights with K={K} do not fit a [hi | lo] operand with segments of {a_seg}")
-        if K == taps * a_width:
-            return dict(K=K, lda=a_width, a_dup_seg=0)
-        if 2 * K == 3 * taps * a_width:
-            return dict(K=K, lda=a_width, a_dup_seg=a_width // 2)
-        if taps == 1 and K == 2 * a_width:     # [w_hi | w_lo] against a plain operand walked twice (weight-only split)
-            return dict(K=K, lda=a_width, a_dup_seg=0, a_wrap=a_width)
-        raise HipExtError(f"packed weights with K={K} do not fit an operand of width {a_width} ({taps} tap(s))")
+    def _mm(A, p: O.Packed, act: O.ActForm, **kw):
+        """One ada_igemm launch: the rows of ``A`` (row stride = its last dimension), written in the form ``act``, against the packed weights ``p``."""
+        k_igemm(A=A, W=p.t, **O.walk(p, act, A.shape[-1]), **kw)
 
     @classmethod
-    def _conv3(cls, src_pad, w, M, N, grid, stride=1, cin=None, k_alg=None, **kw):
-        """3x3 conv over a zero-bordered NHWC tensor (plain or split input, see _kdup)."""
+    def _conv3(cls, src_pad, p, act, M, N, grid, stride=1, cin=None, k_alg=None, **kw):
+        """3x3 conv over a zero-bordered NHWC tensor."""
         B, Hp, Wp, Cp = src_pad.shape
-        kd = cls._kdup(Cp, w, taps=9)
-        k_igemm(M=M, N=N, k_alg=k_alg if k_alg is not None else 9 * (cin or kd.get("a_dup_seg") or kd.get("f8_from") or Cp), A=src_pad, W=w, a_mode=A_CONV3,
-                conv=(grid[0], grid[1], Hp, Wp, stride), **kd, **kw)
+        cls._mm(src_pad, p, act, M=M, N=N, k_alg=k_alg if k_alg is not None else 9 * (cin or p.seg), a_mode=A_CONV3, conv=(grid[0], grid[1], Hp, Wp, stride), **kw)
 
     def forward(self, x: torch.Tensor, guide: Optional[torch.Tensor], normalise: Optional[bool] = None) -> torch.Tensor:
         """One forward.  ``normalise`` overrides the engine's default for the fused ImageNet normalisation of the input (the
@@ -1069,61 +946,37 @@ class DepthEngine:
         norm = self.normalise_input if norm is None else norm
         mean = (0.485, 0.456, 0.406) if norm else None
         inv_std = (1 / 0.229, 1 / 0.224, 1 / 0.225) if norm else None
-        k_patchify(x, guide if w.guided else None, B, w.guide_channels, H, W, mean, inv_std, ws.a_pe, 2 * w.pe_seg, split=True)
+        k_patchify(x, guide if w.guided else None, B, w.guide_channels, H, W, mean, inv_std, ws.a_pe, ws.a_pe.shape[1], split=True)
         pos = w.pos_embed(ph, pw)
-        k_igemm(M=P, N=D, K=w.pe_k, k_alg=(3 + w.guide_channels) * 196, A=ws.a_pe, lda=2 * w.pe_seg, a_dup_seg=w.pe_seg, W=w.pe_w, bias=w.pe_b, res=pos, ldr=D, res_row_mod=Np, res_row_off=1,
-                flags=EP_BIAS | EP_RESIDUAL, out_f32=ws.x, ldo_f32=D, map_f32=MAP_TOKEN, map_h=Np)
+        self._mm(ws.a_pe, w.pe_w, O.A_HILO, M=P, N=D, k_alg=(3 + w.guide_channels) * 196, bias=w.pe_b, res=pos, ldr=D, res_row_mod=Np, res_row_off=1,
+                 flags=EP_BIAS | EP_RESIDUAL, out_f32=ws.x, ldo_f32=D, map_f32=MAP_TOKEN, map_h=Np)
         k_write_cls(ws.x, B, N, D, w.cls, pos)
 
         # ---- transformer blocks ------------------------------------------------------------------
         taps = TAPS[w.encoder]
-        ldy = ws.y.shape[1]
-
-        def a_ln(blk_, wname):      # A-operand arguments of a linear layer that reads the LayerNorm output ws.y: plain, or [hi | lo] / [hi | lo8 | hi8] in a split block
-            if not blk_["esplit"]:
-                return dict(K=D, lda=ldy)
-            if w.enc_f8:
-                return dict(K=2 * D, lda=ldy, f8_from=D, f8_mid=D + D // 2, f8_scales=blk_[wname.replace("_w", "_f8")])
-            return dict(K=3 * D, lda=ldy, a_dup_seg=D)
-
-        ldo, ldh = ws.o.shape[1], ws.hd.shape[1]
-
-        def a_act(blk_, kin, ld, wname):       # ... that reads the attention output / the MLP hidden (width kin, row stride ld): plain, or the split forms its producer wrote
-            if not blk_["esplit"]:
-                return dict(K=kin, lda=ld)
-            if w.enc_f8:
-                return dict(K=2 * kin, lda=ld, f8_from=kin, f8_mid=kin + kin // 2, f8_scales=blk_[wname.replace("_w", "_f8")])
-            return dict(K=3 * kin, lda=ld, a_dup_seg=kin)
-
-        def seg_act(blk_, kin):     # split_seg of the producer of such an activation
-            return (-kin if w.enc_f8 else kin) if blk_["esplit"] else 0
-
-        def seg(blk_):              # split_seg of the LayerNorm that feeds blk_'s linear layers
-            return (-D if w.enc_f8 else D) if blk_["esplit"] else 0
+        tap_seg = w.act_form("tap").split_seg(D)
+        ldy, ldo, ldh = ws.y.shape[1], ws.o.shape[1], ws.hd.shape[1]
         ln1_done = False    # block i's norm1 output already sits in ws.y (emitted by the tap LayerNorm of block i - 1, see below)
         for i, blk in enumerate(w.blocks):
             last = i == len(w.blocks) - 1
-            if ln1_done:
-                ln1_done = False
-                k_igemm(M=T, N=3 * D, k_alg=D, A=ws.y, W=blk["qkv_w"], bias=blk["qkv_b"], flags=EP_BIAS, out_op=ws.qkv, ldo_op=3 * D, **a_ln(blk, "qkv_w"))
-            else:
-                k_layernorm(ws.x, D, T, D, blk["ln1_w"], blk["ln1_b"], LN_EPS, out_op=ws.y, ld_op=ldy, split_seg=seg(blk))
-                k_igemm(M=T, N=3 * D, k_alg=D, A=ws.y, W=blk["qkv_w"], bias=blk["qkv_b"], flags=EP_BIAS, out_op=ws.qkv, ldo_op=3 * D, **a_ln(blk, "qkv_w"))
-            k_attention(ws.qkv, ws.o, B, N, heads, ld_out=ldo if ldo != D else 0, split_seg=seg_act(blk, D))
+            act = w.act_form(i)     # of the rows this block's four linear layers read: LayerNorm output, attention output, MLP hidden
+            if not ln1_done:
+                k_layernorm(ws.x, D, T, D, blk["ln1_w"], blk["ln1_b"], LN_EPS, out_op=ws.y, ld_op=ldy, split_seg=act.split_seg(D))
+            ln1_done = False
+            self._mm(ws.y, blk["qkv_w"], act, M=T, N=3 * D, k_alg=D, bias=blk["qkv_b"], flags=EP_BIAS, out_op=ws.qkv, ldo_op=3 * D)
+            k_attention(ws.qkv, ws.o, B, N, heads, ld_out=ldo if ldo != D else 0, split_seg=act.split_seg(D))
             hid = blk["hidden"]
-            k_igemm(M=T, N=D, k_alg=D, A=ws.o, W=blk["proj_w"], bias=blk["proj_b"], gamma=blk["ls1"], res=ws.x, ldr=D,
-                    flags=EP_BIAS | EP_GAMMA | EP_RESIDUAL, out_f32=ws.x, ldo_f32=D, **a_act(blk, D, ldo, "proj_w"))
-            k_layernorm(ws.x, D, T, D, blk["ln2_w"], blk["ln2_b"], LN_EPS, out_op=ws.y, ld_op=ldy, split_seg=seg(blk))
+            self._mm(ws.o, blk["proj_w"], act, M=T, N=D, k_alg=D, bias=blk["proj_b"], gamma=blk["ls1"], res=ws.x, ldr=D,
+                     flags=EP_BIAS | EP_GAMMA | EP_RESIDUAL, out_f32=ws.x, ldo_f32=D)
+            k_layernorm(ws.x, D, T, D, blk["ln2_w"], blk["ln2_b"], LN_EPS, out_op=ws.y, ld_op=ldy, split_seg=act.split_seg(D))
             if w.ffn == "mlp":
-                k_igemm(M=T, N=hid, k_alg=D, A=ws.y, W=blk["fc1_w"], bias=blk["fc1_b"], flags=EP_BIAS | EP_GELU,
-                        out_op=ws.hd, ldo_op=ldh, split_seg=seg_act(blk, hid), **a_ln(blk, "fc1_w"))
-                k_igemm(M=T, N=D, k_alg=hid, A=ws.hd, W=blk["fc2_w"], bias=blk["fc2_b"], gamma=blk["ls2"], res=ws.x, ldr=D,
-                        flags=EP_BIAS | EP_GAMMA | EP_RESIDUAL, out_f32=ws.x, ldo_f32=D, **a_act(blk, hid, ldh, "fc2_w"))
+                self._mm(ws.y, blk["fc1_w"], act, M=T, N=hid, k_alg=D, bias=blk["fc1_b"], flags=EP_BIAS | EP_GELU, out_op=ws.hd, ldo_op=ldh, split_seg=act.split_seg(hid))
+                self._mm(ws.hd, blk["fc2_w"], act, M=T, N=D, k_alg=hid, bias=blk["fc2_b"], gamma=blk["ls2"], res=ws.x, ldr=D,
+                         flags=EP_BIAS | EP_GAMMA | EP_RESIDUAL, out_f32=ws.x, ldo_f32=D)
             else:
-                k_igemm(M=T, N=2 * hid, k_alg=D, A=ws.y, W=blk["w12_w"], bias=blk["w12_b"], flags=EP_BIAS | EP_SWIGLU,
-                        out_op=ws.hd, ldo_op=ldh, split_seg=seg_act(blk, hid), **a_ln(blk, "w12_w"))
-                k_igemm(M=T, N=D, k_alg=hid, A=ws.hd, W=blk["w3_w"], bias=blk["w3_b"], gamma=blk["ls2"], res=ws.x, ldr=D,
-                        flags=EP_BIAS | EP_GAMMA | EP_RESIDUAL, out_f32=ws.x, ldo_f32=D, **a_act(blk, hid, ldh, "w3_w"))
+                self._mm(ws.y, blk["w12_w"], act, M=T, N=2 * hid, k_alg=D, bias=blk["w12_b"], flags=EP_BIAS | EP_SWIGLU, out_op=ws.hd, ldo_op=ldh, split_seg=act.split_seg(hid))
+                self._mm(ws.hd, blk["w3_w"], act, M=T, N=D, k_alg=hid, bias=blk["w3_b"], gamma=blk["ls2"], res=ws.x, ldr=D,
+                         flags=EP_BIAS | EP_GAMMA | EP_RESIDUAL, out_f32=ws.x, ldo_f32=D)
             if self.block_probe is not None:      # diagnostic (tools/stage_errors.py): the residual stream behind block i
                 self.block_probe(i, ws)
             if i in taps:  # shared final LayerNorm on the tap, cls row dropped (dinov2.py:337-340)
@@ -1132,16 +985,16 @@ class DepthEngine:
                     # the next block's norm1 (block.py:84) reads the very rows this LayerNorm reads: one pass over x, two outputs with the
                     # same statistics -- norm1(x) for all T rows into ws.y, norm(x) without the cls rows into the tap
                     nb = w.blocks[i + 1]
-                    k_layernorm(ws.x, D, T, D, nb["ln1_w"], nb["ln1_b"], LN_EPS, out_op=ws.y, ld_op=ldy, split_seg=seg(nb), weight2=w.norm_w, bias2=w.norm_b,
-                                out2_op=tap, ld2_op=tap.shape[1], out2_group=N, out2_skip=1, split_seg2=ws.tap_seg)
+                    k_layernorm(ws.x, D, T, D, nb["ln1_w"], nb["ln1_b"], LN_EPS, out_op=ws.y, ld_op=ldy, split_seg=w.act_form(i + 1).split_seg(D), weight2=w.norm_w, bias2=w.norm_b,
+                                out2_op=tap, ld2_op=tap.shape[1], out2_group=N, out2_skip=1, split_seg2=tap_seg)
                     ln1_done = True
                 else:
                     k_layernorm(ws.x, D, P, D, w.norm_w, w.norm_b, LN_EPS, group_in=N, skip=1, out_op=tap, ld_op=tap.shape[1],
-                                split_seg=ws.tap_seg)
+                                split_seg=tap_seg)
                 if w.readout:   # the class token of every image (row b * N of the token matrix): input row stride N * D
                     j = taps.index(i)
                     k_layernorm(ws.x, N * D, B, D, w.norm_w, w.norm_b, LN_EPS, out_op=ws.cls_op[j], ld_op=ws.cls_op[j].shape[1],
-                                split_seg=ws.tap_seg)
+                                split_seg=tap_seg)
 
         return self._head(ws, B) if head else ws
 
@@ -1158,84 +1011,81 @@ class DepthEngine:
         ocp, Fp = ws.ocp, ws.Fp
         first = "ip" if w.amodal_head else "rn"     # the family of the contraction that reads the reassembled maps L[i]
 
-        def S(group, seg):   # split_seg argument of a producer whose CONSUMER (a contraction of `group`) reads [hi | lo] segments of width seg
-            return (-seg if group in w.f8_groups else seg) if group in w.split else 0     # < 0: [hi | lo8 | hi8]
-
+        form = w.act_form     # reader -> the form of the buffer it reads: the producer's split_seg and the consumer's walk both come from it
         taps_in = ws.taps
         if w.readout:   # x = GELU(W_x x + (W_cls cls_b + b))  per image (DA2/dpt.py:164-167)
-            KDr = ws.taps[0].shape[1]
             Np = ph * pw
             for i in range(4):
-                k_igemm(M=B, N=D, k_alg=D, A=ws.cls_op[i], W=w.ro_wc[i], bias=w.ro_b[i], flags=EP_BIAS, out_f32=ws.cls_bias[i], ldo_f32=D, **self._kdup(KDr, w.ro_wc[i], a_seg=ws.tap_seg))
+                self._mm(ws.cls_op[i], w.ro_wc[i], form("tap"), M=B, N=D, k_alg=D, bias=w.ro_b[i], flags=EP_BIAS, out_f32=ws.cls_bias[i], ldo_f32=D)
                 # one launch for the whole batch: the bias vector of row m is cls_bias[m // Np] (ada_igemm_args.bias_row_mod)
-                k_igemm(M=B * Np, N=D, k_alg=D, A=ws.taps[i], W=w.ro_wx[i], bias=ws.cls_bias[i], bias_row_mod=Np, **self._kdup(KDr, w.ro_wx[i], a_seg=ws.tap_seg),
-                        flags=EP_BIAS | EP_GELU, out_op=ws.taps_ro[i], ldo_op=ws.taps_ro[i].shape[1], split_seg=S("proj", D))
+                self._mm(ws.taps[i], w.ro_wx[i], form("tap"), M=B * Np, N=D, k_alg=D, bias=ws.cls_bias[i], bias_row_mod=Np,
+                         flags=EP_BIAS | EP_GELU, out_op=ws.taps_ro[i], ldo_op=ws.taps_ro[i].shape[1], split_seg=form("proj").split_seg(D))
             taps_in = ws.taps_ro
         # ---- per level i: reassemble (1x1 project + resize, dpt.py:171-173) -> [amodal: input_projection = conv3x3 -> channels-first LN -> ReLU,
         #      dpt.py:153-159,178-179] -> layerN_rn (blocks.py:20-24): fp32 copy for the residual adds + ReLU'd operand copy for conv1.  The four chains are
         #      independent (chain(i) below touches level-i buffers only) -----
-        KD = ws.taps[0].shape[1]
+
+        def project(i, out, reader, **kw):      # projects[i] of the tap into ``out``, in the form ``reader`` needs
+            self._mm(taps_in[i], w.proj_w[i], form("tap"), M=P, N=oc[i], k_alg=D, bias=w.proj_b[i], flags=EP_BIAS, out_op=out, ldo_op=out.shape[-1],
+                     split_seg=form(reader).split_seg(ocp[i]), **kw)
 
         def reassemble(i):
-            if i < 2:
+            if i in w.sp:     # 1x1 project -> zero-bordered patch-grid tensor; the transposed conv runs inside the sub-pixel convolution below
+                project(i, ws.tp[i], f"sp{i}", map_op=MAP_PAD, map_h=ph, map_w=pw)
+            elif i < 2:
                 s_ = 4 if i == 0 else 2
-                if i in w.sp:     # 1x1 project -> zero-bordered patch-grid tensor; the transposed conv runs inside the sub-pixel convolution below
-                    k_igemm(M=P, N=oc[i], k_alg=D, A=taps_in[i], W=w.proj_w[i], **self._kdup(KD, w.proj_w[i], a_seg=ws.tap_seg), bias=w.proj_b[i], flags=EP_BIAS,
-                            out_op=ws.tp[i], ldo_op=ws.tp[i].shape[3], map_op=MAP_PAD, map_h=ph, map_w=pw, split_seg=-ocp[i] if w.sp[i].get("split") else 0)
-                    return
                 t = ws.t0 if i == 0 else ws.t1
                 rs_w, rs_b = (w.rs0_w, w.rs0_b) if i == 0 else (w.rs1_w, w.rs1_b)
-                k_igemm(M=P, N=oc[i], k_alg=D, A=taps_in[i], W=w.proj_w[i], **self._kdup(KD, w.proj_w[i], a_seg=ws.tap_seg), bias=w.proj_b[i], flags=EP_BIAS, out_op=t, ldo_op=t.shape[1], split_seg=S(f"rs{i}", ocp[i]))
-                k_igemm(M=P, N=s_ * s_ * oc[i], k_alg=oc[i], A=t, W=rs_w, bias=rs_b, flags=EP_BIAS, **self._kdup(t.shape[1], rs_w),
-                        out_op=ws.L[i], ldo_op=ws.L[i].shape[3], map_op=MAP_SHUFFLE, map_h=ph, map_w=pw, shuffle_s=s_, shuffle_c=oc[i], split_seg=S(f"{first}{i}", ocp[i]))
+                project(i, t, f"rs{i}")
+                self._mm(t, rs_w, form(f"rs{i}"), M=P, N=s_ * s_ * oc[i], k_alg=oc[i], bias=rs_b, flags=EP_BIAS,
+                         out_op=ws.L[i], ldo_op=ws.L[i].shape[3], map_op=MAP_SHUFFLE, map_h=ph, map_w=pw, shuffle_s=s_, shuffle_c=oc[i], split_seg=form(f"{first}{i}").split_seg(ocp[i]))
             elif i == 2:
-                k_igemm(M=P, N=oc[2], k_alg=D, A=taps_in[2], W=w.proj_w[2], **self._kdup(KD, w.proj_w[2], a_seg=ws.tap_seg), bias=w.proj_b[2], flags=EP_BIAS,
-                        out_op=ws.L[2], ldo_op=ws.L[2].shape[3], map_op=MAP_PAD, map_h=ph, map_w=pw, split_seg=S(first + "2", ocp[2]))
+                project(2, ws.L[2], first + "2", map_op=MAP_PAD, map_h=ph, map_w=pw)
             else:
-                k_igemm(M=P, N=oc[3], k_alg=D, A=taps_in[3], W=w.proj_w[3], **self._kdup(KD, w.proj_w[3], a_seg=ws.tap_seg), bias=w.proj_b[3], flags=EP_BIAS,
-                        out_op=ws.pre3, ldo_op=ws.pre3.shape[3], map_op=MAP_PAD, map_h=ph, map_w=pw, split_seg=S("rs3", ocp[3]))
-                self._conv3(ws.pre3, w.rs3_w, rows[3], oc[3], grid[3], stride=2, cin=oc[3], bias=w.rs3_b, flags=EP_BIAS,
-                            out_op=ws.L[3], ldo_op=ws.L[3].shape[3], map_op=MAP_PAD, map_h=grid[3][0], map_w=grid[3][1], split_seg=S(first + "3", ocp[3]))
+                project(3, ws.pre3, "rs3", map_op=MAP_PAD, map_h=ph, map_w=pw)
+                self._conv3(ws.pre3, w.rs3_w, form("rs3"), rows[3], oc[3], grid[3], stride=2, cin=oc[3], bias=w.rs3_b, flags=EP_BIAS,
+                            out_op=ws.L[3], ldo_op=ws.L[3].shape[3], map_op=MAP_PAD, map_h=grid[3][0], map_w=grid[3][1], split_seg=form(first + "3").split_seg(ocp[3]))
 
         def input_projection(i):      # amodal only
+            rn_seg = form(f"rn{i}").split_seg(ocp[i])
             if i in w.sp:
                 # resize_layers[i] + input_projection[i][0] as one sub-pixel convolution over the patch grid: [P, s*s*oc] fp32, column block
                 # (py*s + px) = output phase; the LayerNorm reads it in fine-pixel order and takes the transposed conv's bias back out where
                 # a tap falls into the zero padding (the outermost ring of the fine grid)
                 sp = w.sp[i]
                 ncol = sp["s"] * sp["s"] * oc[i]
-                self._conv3(ws.tp[i], sp["w"], P, ncol, (ph, pw), k_alg=sp["taps_per_col"] * oc[i], bias=sp["b"], flags=EP_BIAS,
+                self._conv3(ws.tp[i], sp["w"], form(f"sp{i}"), P, ncol, (ph, pw), k_alg=sp["taps_per_col"] * oc[i], bias=sp["b"], flags=EP_BIAS,
                             out_f32=ws.ipf[i], ldo_f32=ncol, tap_cols=oc[i], tap_mask=sp["masks"])
                 k_layernorm(ws.ipf[i], ncol, rows[i], oc[i], w.ip_ln_w[i], w.ip_ln_b[i], LN_EPS, out_op=ws.L2[i], ld_op=ws.L2[i].shape[3],
-                            map_op=MAP_PAD, map_h=grid[i][0], map_w=grid[i][1], relu=True, split_seg=S(f"rn{i}", ocp[i]),
-                            unshuffle_s=sp["s"], tap_bias=sp["tapb"])
+                            map_op=MAP_PAD, map_h=grid[i][0], map_w=grid[i][1], relu=True, split_seg=rn_seg, unshuffle_s=sp["s"], tap_bias=sp["tapb"])
                 return
-            self._conv3(ws.L[i], w.ip_w[i], rows[i], oc[i], grid[i], cin=oc[i], bias=w.ip_b[i], flags=EP_BIAS, out_f32=ws.ipf[i], ldo_f32=oc[i])
+            self._conv3(ws.L[i], w.ip_w[i], form(f"ip{i}"), rows[i], oc[i], grid[i], cin=oc[i], bias=w.ip_b[i], flags=EP_BIAS, out_f32=ws.ipf[i], ldo_f32=oc[i])
             k_layernorm(ws.ipf[i], oc[i], rows[i], oc[i], w.ip_ln_w[i], w.ip_ln_b[i], LN_EPS, out_op=ws.L2[i],
-                        ld_op=ws.L2[i].shape[3], map_op=MAP_PAD, map_h=grid[i][0], map_w=grid[i][1], relu=True, split_seg=S(f"rn{i}", ocp[i]))
+                        ld_op=ws.L2[i].shape[3], map_op=MAP_PAD, map_h=grid[i][0], map_w=grid[i][1], relu=True, split_seg=rn_seg)
 
         def layer_rn(i):
+            rcu_seg = form(f"rcu{i}").split_seg(Fp)
             if not w.amodal_head and i in w.sp:
                 # raw head: resize_layers[i] + layer{i+1}_rn as one sub-pixel convolution over the patch grid, then ONE re-layout pass: fine-pixel
                 # order, the transposed conv's bias taken out on the outermost ring, fp32 copy for the residual adds + ReLU'd operand copy
                 sp = w.sp[i]
                 ncol = sp["s"] * sp["s"] * Fch
-                self._conv3(ws.tp[i], sp["w"], P, ncol, (ph, pw), k_alg=sp["taps_per_col"] * oc[i], bias=sp["b"], flags=EP_BIAS,
+                self._conv3(ws.tp[i], sp["w"], form(f"sp{i}"), P, ncol, (ph, pw), k_alg=sp["taps_per_col"] * oc[i], bias=sp["b"], flags=EP_BIAS,
                             out_f32=ws.spf[i], ldo_f32=ncol, tap_cols=Fch, tap_mask=sp["masks"])
                 k_layernorm(ws.spf[i], ncol, rows[i], Fch, None, None, LN_EPS, identity=True, relu=2, out_f32=ws.rnx[i], ld_f32=Fch, out_op=ws.rnr[i],
-                            ld_op=ws.rnr[i].shape[3], map_op=MAP_PAD, map_h=grid[i][0], map_w=grid[i][1], split_seg=S(f"rcu{i}", Fp),
+                            ld_op=ws.rnr[i].shape[3], map_op=MAP_PAD, map_h=grid[i][0], map_w=grid[i][1], split_seg=rcu_seg,
                             unshuffle_s=sp["s"], tap_bias=sp["tapb"])
                 return
             src = ws.L2[i] if w.amodal_head else ws.L[i]
-            self._conv3(src, w.rn_w[i], rows[i], Fch, grid[i], cin=oc[i], flags=EP_RELU_OP, out_f32=ws.rnx[i], ldo_f32=Fch,
-                        out_op=ws.rnr[i], ldo_op=ws.rnr[i].shape[3], map_op=MAP_PAD, map_h=grid[i][0], map_w=grid[i][1], split_seg=S(f"rcu{i}", Fp))
+            self._conv3(src, w.rn_w[i], form(f"rn{i}"), rows[i], Fch, grid[i], cin=oc[i], flags=EP_RELU_OP, out_f32=ws.rnx[i], ldo_f32=Fch,
+                        out_op=ws.rnr[i], ldo_op=ws.rnr[i].shape[3], map_op=MAP_PAD, map_h=grid[i][0], map_w=grid[i][1], split_seg=rcu_seg)
 
         def rcu(i, fw, unit, src_relu_pad, src_f32, **out):
             """ResidualConvUnit (blocks.py:57-80) at grid i: conv2(relu(conv1(relu(x)))) + x."""
-            g = grid[i]
-            self._conv3(src_relu_pad, fw[f"u{unit}c1_w"], rows[i], Fch, g, cin=Fch, bias=fw[f"u{unit}c1_b"], flags=EP_BIAS | EP_RELU_OP,
-                        out_op=ws.tmpa[i], ldo_op=ws.tmpa[i].shape[3], map_op=MAP_PAD, map_h=g[0], map_w=g[1], split_seg=S(f"rcu{i}", Fp))
-            self._conv3(ws.tmpa[i], fw[f"u{unit}c2_w"], rows[i], Fch, g, cin=Fch, bias=fw[f"u{unit}c2_b"], res=src_f32, ldr=Fch,
+            g, act = grid[i], form(f"rcu{i}")
+            self._conv3(src_relu_pad, fw[f"u{unit}c1_w"], act, rows[i], Fch, g, cin=Fch, bias=fw[f"u{unit}c1_b"], flags=EP_BIAS | EP_RELU_OP,
+                        out_op=ws.tmpa[i], ldo_op=ws.tmpa[i].shape[3], map_op=MAP_PAD, map_h=g[0], map_w=g[1], split_seg=act.split_seg(Fp))
+            self._conv3(ws.tmpa[i], fw[f"u{unit}c2_w"], act, rows[i], Fch, g, cin=Fch, bias=fw[f"u{unit}c2_b"], res=src_f32, ldr=Fch,
                         flags=EP_BIAS | EP_RESIDUAL, **out)
 
         def chain(i):     # everything of level i that does not depend on another level; RCU 1 of levels 0-2 (blocks.py:131-133) reads rnr / rnx of its own level only
@@ -1268,34 +1118,30 @@ class DepthEngine:
         s_f32, s_pad = ws.rnx[3], ws.rnr[3]
         for i in (3, 2, 1, 0):
             fw = w.fuse[i]
-            rcu(i, fw, 2, s_pad, s_f32, out_op=ws.u[i], ldo_op=ws.u[i].shape[1], split_seg=S(f"out{i}", Fp))
+            rcu(i, fw, 2, s_pad, s_f32, out_op=ws.u[i], ldo_op=ws.u[i].shape[1], split_seg=form(f"out{i}").split_seg(Fp))
             if i == 0 and w.oc1c is not None:
                 break     # refinenet1.out_conv is part of output_conv1's tap maps (below)
-            k_igemm(M=rows[i], N=Fch, k_alg=Fch, A=ws.u[i], W=fw["out_w"], bias=fw["out_b"], flags=EP_BIAS, **self._kdup(ws.u[i].shape[1], fw["out_w"]),
-                    out_f32=ws.zf[i], ldo_f32=Fch)
+            self._mm(ws.u[i], fw["out_w"], form(f"out{i}"), M=rows[i], N=Fch, k_alg=Fch, bias=fw["out_b"], flags=EP_BIAS, out_f32=ws.zf[i], ldo_f32=Fch)
             if i > 0:
                 j = i - 1
                 k_bilinear(ws.zf[i], Fch, B, grid[i][0], grid[i][1], grid[j][0], grid[j][1], Fch, add=ws.r[j], ld_add=Fch,
-                           out_f32=ws.s[j], ld_f32=Fch, out_op=ws.sr[j], ld_op=ws.sr[j].shape[3], map_op=MAP_PAD, relu=True, split_seg=S(f"rcu{j}", Fp))
+                           out_f32=ws.s[j], ld_f32=Fch, out_op=ws.sr[j], ld_op=ws.sr[j].shape[3], map_op=MAP_PAD, relu=True, split_seg=form(f"rcu{j}").split_seg(Fp))
                 s_f32, s_pad = ws.s[j], ws.sr[j]
         g2 = ws.g296
         # ---- resize x2 -> output_conv1 (dpt.py:192-193) -> resize to (14 ph, 14 pw) -> output_conv2 (3x3, ReLU, 1x1, activation) (:194-195) ----
         if w.oc1c is not None:
             ntap = 9 * ws.half
-            if "f8" in w.oc1c:      # u[0] is [hi | lo8 | hi8] (split group "out0"): a full split product with fp8 correction terms
-                k_igemm(M=rows[0], N=ntap, K=2 * Fp, k_alg=Fch, A=ws.u[0], lda=ws.u[0].shape[1], W=w.oc1c["w"], f8_from=Fp, f8_mid=Fp + Fp // 2, f8_scales=w.oc1c["f8"],
-                        bias=w.oc1c["b"], flags=EP_BIAS, out_op=ws.tmaps, ldo_op=ntap)
-            else:
-                k_igemm(M=rows[0], N=ntap, K=2 * Fp, a_wrap=Fp, k_alg=Fch, A=ws.u[0], lda=Fp, W=w.oc1c["w"], bias=w.oc1c["b"], flags=EP_BIAS, out_op=ws.tmaps, ldo_op=ntap)
+            # u[0] plain against [w_hi | w_lo], or (split group "out0") [hi | lo8 | hi8]: a full split product with fp8 correction terms
+            self._mm(ws.u[0], w.oc1c["w"], form("out0"), M=rows[0], N=ntap, k_alg=Fch, bias=w.oc1c["b"], flags=EP_BIAS, out_op=ws.tmaps, ldo_op=ntap)
             k_tapsum_resize(ws.tmaps, ntap, B, grid[0][0], grid[0][1], g2[0], g2[1], ws.half, w.oc1_b, ws.oc1, ws.half)
         else:
-            k_bilinear(ws.zf[0], Fch, B, grid[0][0], grid[0][1], g2[0], g2[1], Fch, out_op=ws.p1, ld_op=ws.p1.shape[3], map_op=MAP_PAD, split_seg=S("oc1", Fp))
-            self._conv3(ws.p1, w.oc1_w, B * g2[0] * g2[1], ws.half, g2, cin=Fch, bias=w.oc1_b, flags=EP_BIAS, out_f32=ws.oc1, ldo_f32=ws.half)
+            k_bilinear(ws.zf[0], Fch, B, grid[0][0], grid[0][1], g2[0], g2[1], Fch, out_op=ws.p1, ld_op=ws.p1.shape[3], map_op=MAP_PAD, split_seg=form("oc1").split_seg(Fp))
+            self._conv3(ws.p1, w.oc1_w, form("oc1"), B * g2[0] * g2[1], ws.half, g2, cin=Fch, bias=w.oc1_b, flags=EP_BIAS, out_f32=ws.oc1, ldo_f32=ws.half)
         out = torch.empty(B, 1, ws.H, ws.W, dtype=torch.float32, device=ws.oc1.device)
         if ws.fused_tail:
-            k_dpt_tail(ws.oc1, ws.half, B, g2[0], g2[1], ws.H, ws.W, ws.halfp, w.oc2_w, w.oc2_b, w.tail_w, w.tail_b, self.final_act, out)
+            k_dpt_tail(ws.oc1, ws.half, B, g2[0], g2[1], ws.H, ws.W, ws.halfp, w.oc2_w.t, w.oc2_b, w.tail_w, w.tail_b, self.final_act, out)
             return out
-        k_bilinear(ws.oc1, ws.half, B, g2[0], g2[1], ws.H, ws.W, ws.half, out_op=ws.fin, ld_op=ws.fin.shape[3], map_op=MAP_PAD, split_seg=S("oc2", ws.halfp))
-        self._conv3(ws.fin, w.oc2_w, B * ws.H * ws.W, w.oc2_w.shape[0], (ws.H, ws.W), cin=ws.half, bias=w.oc2_b, flags=EP_BIAS | EP_TAIL,
+        k_bilinear(ws.oc1, ws.half, B, g2[0], g2[1], ws.H, ws.W, ws.half, out_op=ws.fin, ld_op=ws.fin.shape[3], map_op=MAP_PAD, split_seg=form("oc2").split_seg(ws.halfp))
+        self._conv3(ws.fin, w.oc2_w, form("oc2"), B * ws.H * ws.W, w.oc2_w.t.shape[0], (ws.H, ws.W), cin=ws.half, bias=w.oc2_b, flags=EP_BIAS | EP_TAIL,
                     out_f32=out, ldo_f32=1, tail_w=w.tail_w, tail_b=w.tail_b, tail_act=self.final_act)
         return out

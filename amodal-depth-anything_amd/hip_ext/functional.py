@@ -19,6 +19,7 @@ from . import bilinear as k_bilinear
 from . import igemm as k_igemm
 from . import layernorm as k_layernorm
 from . import operand_dtype
+from . import operands as O
 from . import patchify as k_patchify
 
 
@@ -275,13 +276,11 @@ def compose_f32(a, b):
     N = b.shape[0]
     kp, np_ = _r64(K), (N + 3) // 4 * 4
     a32 = F.pad(a.detach().float(), (0, kp - K))
-    b32 = F.pad(b.detach().float(), (0, kp - K, 0, np_ - N))
     a_hi = a32.to(op)
-    b_hi = b32.to(op)
     A = torch.cat([a_hi, (a32 - a_hi.float()).to(op)], dim=1).contiguous()
-    Wp = torch.cat([b_hi, b_hi, (b32 - b_hi.float()).to(op)], dim=1).contiguous()
+    Wp = O.pack(F.pad(b.detach().float(), (0, 0, 0, np_ - N)), O.W_SPLIT3, op)
     out = torch.empty(M, np_, dtype=torch.float32, device=a.device)
-    k_igemm(M=M, N=np_, K=3 * kp, A=A, lda=2 * kp, a_dup_seg=kp, W=Wp, flags=0, out_f32=out, ldo_f32=np_)
+    k_igemm(M=M, N=np_, A=A, W=Wp.t, flags=0, out_f32=out, ldo_f32=np_, **O.walk(Wp, O.A_HILO, A.shape[1]))
     return out[:, :N] if np_ != N else out
 
 

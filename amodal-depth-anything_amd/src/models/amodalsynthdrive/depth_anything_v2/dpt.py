@@ -325,8 +325,8 @@ class _EngineMixin:
             # in split precision.
             mode = getattr(self, "head_precision", "auto")
             # ONE decision for everything that touches the fp8 form on the sigmoid ViT-B / ViT-L models (with module.f8_terms = "none" / "enc"
-            # the first rung's "proj" split, the taps' [hi | lo8 | hi8] form and the fp16-packed weights used to be derived separately and met in _kdup
-            # as "three-term fp16 weights against a [hi | lo8 | hi8] operand"): the caller's f8_terms, when given, rules the first rung's projects, the
+            # the first rung's "proj" split, the taps' [hi | lo8 | hi8] form and the fp16-packed weights used to be derived separately and met at launch
+            # as "three-term fp16 weights against a [hi | lo8 | hi8] operand"; PackedWeights now refuses the pair when it packs): the caller's f8_terms, when given, rules the first rung's projects, the
             # second rung's weights, the form of the taps between them and the third rung alike.
             f8_user = getattr(self, "f8_terms", None)
             head_f8_ok = f8_user is None or f8_user in ("head", "both")
