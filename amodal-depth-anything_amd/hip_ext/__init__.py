@@ -28,7 +28,7 @@ ACT_NONE, ACT_SIGMOID, ACT_RELU = 0, 1, 2
 EXPORTS = (
     "ada_abi_version", "ada_operand_dtype", "ada_last_error", "ada_igemm", "ada_attention_fwd", "ada_attention_ex",
     "ada_pos_embed_resize", "ada_layernorm_fwd", "ada_layernorm_ex", "ada_patchify", "ada_write_cls", "ada_bilinear_fwd", "ada_selftest",
-    "ada_minmax_fwd", "ada_depth_stats_fwd", "ada_token_diversity_fwd", "ada_normalize_fwd", "ada_blend_fwd", "ada_depth_eval_fwd", "ada_protocol_fit_fwd", "ada_protocol_eval_fwd", "ada_tile_blend_fwd", "ada_dpt_tail_fwd", "ada_tapsum_resize_fwd",
+    "ada_minmax_fwd", "ada_depth_stats_fwd", "ada_token_diversity_fwd", "ada_ladder_select_fwd", "ada_normalize_fwd", "ada_blend_fwd", "ada_depth_eval_fwd", "ada_protocol_fit_fwd", "ada_protocol_eval_fwd", "ada_tile_blend_fwd", "ada_dpt_tail_fwd", "ada_tapsum_resize_fwd",
     "ada_image_prep_fwd", "ada_depth_resize_fwd",
     "ada_photo_prep_fwd", "ada_mask_prep_fwd", "ada_nearest_resize_fwd", "ada_blend_ex", "ada_depth_render_fwd",
     "ada_pil_resize_u8_fwd", "ada_label_combine_fwd",
@@ -141,6 +141,9 @@ def load(path: Optional[str] = None):
     lib.ada_depth_stats_fwd.restype = c_int
     lib.ada_token_diversity_fwd.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]
     lib.ada_token_diversity_fwd.restype = c_int
+    lib.ada_ladder_select_fwd.argtypes = [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_double, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.ada_ladder_select_fwd.restype = c_int
     lib.ada_normalize_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
     lib.ada_normalize_fwd.restype = c_int
     lib.ada_blend_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]
@@ -404,6 +407,41 @@ def token_diversity(tap, ld, batch, rows_per_image, dim, sums):
     """tap: operand-typed [batch * rows_per_image, ld] -> sums fp32 [batch, ceil(dim / 64), 2] = per column chunk (sum Var_rows, sum E_rows[t^2]) (ada_token_diversity_fwd)."""
     _check(load().ada_token_diversity_fwd(_dev(tap, "tap", operand_dtype()), ld, batch, rows_per_image, dim, _dev(sums, "sums", torch.float32), _stream()),
            "ada_token_diversity_fwd")
+
+
+def ladder_select(stat_sums, stat_div, stat_in, thr, thr3, div, div_in, has2, has3, has_r, out, src2, src3, rung, ratio, counts):
+    """The precision ladder's decision and paste on the device (ada_ladder_select_fwd; the rule is hip_ext.ladder.ladder_decide with ran = 1, fed by
+    hip_ext.ladder.stats_from_host's arithmetic).  stat_sums fp32 [B, chunks, 2]; stat_div / stat_in fp32 [B, G, 2] or None; thresholds as Python floats
+    (inf = none); out fp32 [B, ...] contiguous, updated in place; src2 / src3 fp32 of out's shape or None; rung int32 [B], ratio float64 [B] (overwritten),
+    counts int64 [4] (added to: calls, images on rung >= 2, on rung 3, unserved).  No host read, no allocation: capturable."""
+    B = out.shape[0]
+    n = out.numel() // max(B, 1)
+
+    def block(t, name):
+        if t is None:
+            return None, 0
+        if t.dim() != 3 or t.shape[0] != B or t.shape[2] != 2 or not t.is_contiguous():
+            raise HipExtError(f"ladder_select: {name} must be a contiguous [B={B}, n, 2] tensor, got {tuple(t.shape)}")
+        return _dev(t, name, torch.float32), t.shape[1]
+
+    def rows(t, name):
+        if t is None:
+            return None
+        if t.numel() != out.numel() or not t.is_contiguous():
+            raise HipExtError(f"ladder_select: {name} must be contiguous and as large as out ({out.numel()} elements), got {t.numel()}")
+        return _dev(t, name, torch.float32)
+    if not out.is_contiguous() or B < 1 or n < 1:
+        raise HipExtError(f"ladder_select: out must be a non-empty contiguous [B, ...] tensor, got {tuple(out.shape)}")
+    for t, name, k in ((rung, "rung", B), (ratio, "ratio", B), (counts, "counts", 4)):
+        if t.numel() != k or not t.is_contiguous():
+            raise HipExtError(f"ladder_select: {name} must hold {k} contiguous elements, got {tuple(t.shape)}")
+    if stat_sums is None and has_r:
+        raise HipExtError("ladder_select: has_r without stat_sums")
+    (p_sums, chunks), (p_div, groups), (p_in, groups_in) = block(stat_sums, "stat_sums"), block(stat_div, "stat_div"), block(stat_in, "stat_in")
+    _check(load().ada_ladder_select_fwd(p_sums, chunks, p_div, groups, p_in, groups_in, B, float(thr), float(thr3), float(div), float(div_in),
+                                        int(bool(has2)), int(bool(has3)), int(bool(has_r)), _dev(out, "out", torch.float32), rows(src2, "src2"), rows(src3, "src3"), n,
+                                        _dev(rung, "rung", torch.int32), _dev(ratio, "ratio", torch.float64), _dev(counts, "counts", torch.int64), _stream()),
+           "ada_ladder_select_fwd")
 
 
 def normalize(inp, minmax_in, norm=None, obs=None):

@@ -36,12 +36,13 @@ from . import layernorm as _layernorm
 from . import debug_epoch, instrumented, operand_dtype
 from . import depth_stats as k_depth_stats
 from . import token_diversity as k_token_diversity
+from . import ladder_select as k_ladder_select
 from . import patchify as k_patchify
 from . import pos_embed_resize as k_pos_embed_resize
 from . import tapsum_resize as k_tapsum_resize
 from . import write_cls as k_write_cls
 from . import operands as O
-from .ladder import ladder_curve, ladder_decide, ladder_thresholds, next_start_rung, rung_counts  # noqa: F401  (ladder_curve: re-exported)
+from .ladder import ladder_curve, ladder_decide, ladder_thresholds, next_start_rung, rung_counts, stats_from_host  # noqa: F401  (ladder_curve: re-exported)
 from .operands import f8_weight_split  # noqa: F401  (re-exported)
 
 _probe = None   # list of (label, device counter) while DepthEngine.saturation_report runs, else None
@@ -571,6 +572,12 @@ class DepthEngine:
         self.last_ratio = None        # per-image sum s(1-s) / sum s of the most recent call (CPU tensor), None when the ladder is off
         self.last_diversity = None    # per-image token diversity of the last tap (see _image_stats)
         self.last_input_diversity = None   # ... and of the patchified input
+        # device mode of the ladder (forward(on_device=...), _ladder_device): per image the rung and r of the most recent such call and the running
+        # counts (calls, images on rung >= 2, on rung 3, unserved), all ON THE DEVICE -- read with device_ladder_report(), which is what synchronises
+        self.last_rungs_dev: Optional[torch.Tensor] = None
+        self.last_ratio_dev: Optional[torch.Tensor] = None
+        self.ladder_counts_dev: Optional[torch.Tensor] = None
+        self._dev_state: Dict[tuple, tuple] = {}     # (B, device) -> (rung int32 [B], ratio float64 [B], counts int64 [4]); never dropped: captured graphs hold their addresses
         self._ws: "OrderedDict[tuple, Workspace]" = OrderedDict()
         self._graphs: "OrderedDict[tuple, object]" = OrderedDict()   # key -> _GraphedForward | False (capture refused) | int (sightings)
         self._lock = threading.Lock()
@@ -628,20 +635,28 @@ class DepthEngine:
         B, Hp, Wp, Cp = src_pad.shape
         cls._mm(src_pad, p, act, M=M, N=N, k_alg=k_alg if k_alg is not None else 9 * (cin or p.seg), a_mode=A_CONV3, conv=(grid[0], grid[1], Hp, Wp, stride), **kw)
 
-    def forward(self, x: torch.Tensor, guide: Optional[torch.Tensor], normalise: Optional[bool] = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, guide: Optional[torch.Tensor], normalise: Optional[bool] = None, on_device=False) -> torch.Tensor:
         """One forward.  ``normalise`` overrides the engine's default for the fused ImageNet normalisation of the input (the
         patchify kernel applies (x - mean) / std on the fly: callers holding a [0, 1] image need no separate normalise pass).  The smallest problems are bound by the host's launch rate (~230 launches per image): for those the launch
-        sequence is captured once per input shape into a HIP graph and replayed, bit-identically (``ADA_GRAPH`` = auto | 1 | 0)."""
+        sequence is captured once per input shape into a HIP graph and replayed, bit-identically (``ADA_GRAPH`` = auto | 1 | 0).
+        ``on_device`` = False | True | "head": the precision ladder in its device mode (_ladder_device) -- every rung for the whole batch, the decision taken by a
+        kernel, no host read: the only form of the ladder that runs inside a caller's stream capture.  Ignored by an engine without a ladder."""
         if not x.is_cuda:
             raise HipExtError("DepthEngine.forward: input must live on a HIP device (no CPU fallback in the product path)")
+        if on_device not in (False, True, "head"):
+            raise HipExtError(f"DepthEngine.forward: on_device={on_device!r} (False | True | 'head')")
         norm = self.normalise_input if normalise is None else bool(normalise)
+        if on_device is not False and self.ladder is not None:
+            ladder = (lambda x_, g_, first=None: self._ladder_device(x_, g_, norm, on_device, first=first))
+        else:
+            ladder = (lambda x_, g_, first=None: self._ladder(x_, g_, norm, first=first))
         mode = GRAPH_MODE
         # (round 6: with the head's branches on side streams the plain launches of a single ViT-B / ViT-L image are FASTER than the replay -- 2.68 / 5.27 ms against
         #  3.00 / 5.84 ms, profiles/r06_g_* -- so "auto" replays only the model that is bound by the host's launch rate: ViT-S)
         use = mode == "1" or (mode == "auto" and self.w.encoder in GRAPH_AUTO_ENCODERS and x.shape[0] * x.shape[-2] * x.shape[-1] <= GRAPH_AUTO_PIXELS)
         # replay bypasses the Python wrappers: with a KernelTimer or a tile log attached the launches must be issued one by one
         if not use or instrumented() or torch.cuda.is_current_stream_capturing():
-            return self._ladder(x, guide, norm)
+            return ladder(x, guide)
         # the kernel variant / tile override / fused-tail switch in force at capture time are baked into the graph
         key = (tuple(x.shape), None if guide is None else tuple(guide.shape), str(x.device), debug_epoch(), FUSED_TAIL, SUBPIXEL, OC1_COMMUTE, norm)
         with self._lock:
@@ -664,8 +679,8 @@ class DepthEngine:
                 while len(self._graphs) > max(1, MAX_GRAPHS):
                     self._graphs.popitem(last=False)
         if g is False:
-            return self._ladder(x, guide, norm)
-        return g(x, guide, (lambda ws_, out_, x_, g_: self._ladder(x_, g_, norm, first=(ws_, out_))) if self.ladder is not None else None)
+            return ladder(x, guide)
+        return g(x, guide, (lambda ws_, out_, x_, g_: ladder(x_, g_, first=(ws_, out_))) if self.ladder is not None else None)
 
     # ---- precision ladder: the rungs run here, every decision is hip_ext.ladder's ----------------------
     def _second_weights(self) -> PackedWeights:
@@ -714,20 +729,7 @@ class DepthEngine:
         if has_in:
             k_token_diversity(ws.a_pe, ws.a_pe.shape[1], B, ws.ph * ws.pw, eng.w.pe_seg, ws.stat_in)
         host = ws.stat_buf.cpu().double()
-        nst, ndv = B * STAT_CHUNKS * 2, B * ((D + 63) // 64) * 2
-        st = host[:nst].view(B, STAT_CHUNKS, 2).sum(1)
-        r = st[:, 1] / st[:, 0].clamp_min(1e-300) if has_r else torch.zeros(B, dtype=torch.float64)
-        flat = torch.zeros(B, dtype=torch.bool)
-        tap_div = in_div = None
-        if has_div:
-            dv = host[nst:nst + ndv].view(B, -1, 2).sum(1)
-            tap_div = dv[:, 0] / dv[:, 1].clamp_min(1e-300)
-            flat = tap_div < lad["div"]
-        if has_in:      # every patch of the image alike: variance over patches below 1e-4 of their mean square
-            di = host[nst + ndv:].view(B, -1, 2).sum(1)
-            in_div = di[:, 0] / di[:, 1].clamp_min(1e-300)
-            flat = flat | (in_div < lad.get("div_in", 1e-4))
-        return r, flat, tap_div, in_div
+        return stats_from_host(host, B, STAT_CHUNKS, (D + 63) // 64, has_r, lad["div"] if has_div else None, has_in, lad.get("div_in", 1e-4))
 
     def _depth_sums(self, out: torch.Tensor, sums: torch.Tensor):
         """The one launch of ada_depth_stats_fwd for the ladder: (sum |f|, sum w) of every image of ``out`` in STAT_CHUNKS chunks."""
@@ -838,6 +840,71 @@ class DepthEngine:
                           f"r up to {float(ratio.max()):.3g} against thresholds {lad.get('r')} / {lad.get('r3')}; counted in DepthEngine.escalated / escalated3 "
                           "(this message appears once per engine; module.precision_ladder = False switches the ladder off)")
         return out
+
+    def _ladder_device(self, x: torch.Tensor, guide: Optional[torch.Tensor], norm: Optional[bool], mode, first=None) -> torch.Tensor:
+        """The ladder in its DEVICE mode: the data-independent form of _ladder.  The first rung for the batch, the three statistics launches
+        of _image_stats, then EVERY further rung the ladder has for the whole batch -- the second rung's head from the first rung's taps, the third-rung engine's
+        forward -- and one launch of ada_ladder_select_fwd, which takes ladder_decide(r, flat, lad, 1, .) per image from the statistics where they lie and pastes the
+        image's rows from the output of its rung into the first rung's output, which is returned.  A fixed launch sequence with no host read: it runs inside a
+        caller's stream capture, and every image carries the bits of the rung the eager ladder names for it.  The price is every rung for every image, every call.
+        ``mode`` "head": rungs 1 and 2 only -- no third engine is built (no second full-batch workspace); an image that decides 3 carries the second rung's rows
+        (the first's on a ladder without a second rung) and is counted as unserved.  The thresholds enter the launch by value, as ``self.ladder`` holds them now.
+        Nothing is decided in Python: escalated / escalated3 / _start_rung / last_ratio do not move; rung, r and the running counts stay on the device
+        (last_rungs_dev, last_ratio_dev, ladder_counts_dev; device_ladder_report() reads them).  Under capture everything must exist already: a warm-up call in
+        the same mode and shape outside the capture builds the second rung's weights, the third engine, the workspaces and the device tensors.
+        ``first``: as for _ladder (the engine's own graph replay captures the first rung only; the rest follows here as plain launches)."""
+        lad = self.ladder
+        inf = float("inf")
+        B, H, W, dev = x.shape[0], x.shape[-2], x.shape[-1], x.device
+        has2, has3 = "make" in lad, "make3" in lad
+        has_r = "r" in lad or "r3" in lad
+        has_div = lad.get("div", 0.0) > 0.0
+        has_in = self.w.pe_seg // 64 > 0      # Workspace.stat_in
+        run3 = mode != "head" and has3 and (lad.get("r3", inf) < inf or has_div or has_in)
+        skey, wkey = (B, str(dev)), (B, H, W, str(dev))
+        if torch.cuda.is_current_stream_capturing():
+            missing = [what for what, there in (
+                ("the first rung's workspace", wkey in self._ws),
+                ("the second rung's weights and workspace", not has2 or (self._w_hi is not None and (False,) + wkey in self._ws_hi)),
+                ("the third-rung engine and its workspace", not run3 or (self._eng3 is not None and wkey in self._eng3._ws)),
+                ("the device-side rung / ratio / counts tensors", skey in self._dev_state)) if not there]
+            if missing:
+                raise HipExtError(f"precision ladder on the device under stream capture: {', '.join(missing)} not built for a {B}x3x{H}x{W} input -- warm up with one "
+                                  f"forward in the same mode (ladder_on_device = {mode!r}) and shape OUTSIDE the capture (packing and allocating synchronise)")
+        state = self._dev_state.get(skey)
+        if state is None:      # one running count per device, shared by every batch size
+            counts = next((st[2] for k, st in self._dev_state.items() if k[1] == skey[1]), None)
+            state = self._dev_state[skey] = (torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.float64, device=dev),
+                                             counts if counts is not None else torch.zeros(4, dtype=torch.int64, device=dev))
+        rung, ratio, counts = state
+        if first is None:
+            out = self._forward(x, guide, norm)
+            ws = self.workspace(B, H, W, dev)
+        else:
+            ws, out = first
+        # the statistics of the first rung's run: the launches of _image_stats, without its host read
+        if has_r:
+            self._depth_sums(out, ws.stat_sums)
+        if has_div:
+            k_token_diversity(ws.taps[3], ws.taps[3].shape[1], B, ws.ph * ws.pw, self.w.dim, ws.stat_div)
+        if has_in:
+            k_token_diversity(ws.a_pe, ws.a_pe.shape[1], B, ws.ph * ws.pw, self.w.pe_seg, ws.stat_in)
+        src2 = self._head_for(ws, B, None, self._second_weights()) if has2 else None
+        src3 = self._third_engine().forward(x, guide, norm) if run3 else None
+        k_ladder_select(ws.stat_sums if has_r else None, ws.stat_div if has_div else None, ws.stat_in if has_in else None,
+                        lad["r"] if has2 and "r" in lad else inf, lad["r3"] if has3 and "r3" in lad else inf, lad.get("div", 0.0), lad.get("div_in", 1e-4),
+                        has2, has3, has_r, out, src2, src3, rung, ratio, counts)
+        self.last_rungs_dev, self.last_ratio_dev, self.ladder_counts_dev = rung, ratio, counts
+        return out
+
+    def device_ladder_report(self) -> Optional[dict]:
+        """What the device mode of the ladder has left on the device, read NOW (this is the call that synchronises; after a graph replay it shows the replay's
+        values): dict(rungs=int64 [B], ratio=float64 [B] -- of the most recent device-mode call (or replay) of that batch size -- and the running totals calls,
+        escalated, escalated3, unserved since the engine was built).  None before the first device-mode call."""
+        if self.last_rungs_dev is None:
+            return None
+        calls, n2, n3, unserved = (int(v) for v in self.ladder_counts_dev.cpu())
+        return dict(rungs=self.last_rungs_dev.cpu().long(), ratio=self.last_ratio_dev.cpu(), calls=calls, escalated=n2, escalated3=n3, unserved=unserved)
 
     def _head_for(self, ws: Workspace, B: int, idx: Optional[torch.Tensor], w: PackedWeights) -> torch.Tensor:
         """The DPT head with the weights ``w`` (this engine's own = first rung, or the second rung's) for the images ``idx`` (CPU index tensor; None = all B) of the

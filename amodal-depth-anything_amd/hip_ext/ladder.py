@@ -65,6 +65,31 @@ def ladder_thresholds(z1: torch.Tensor, z2: Optional[torch.Tensor], z3: torch.Te
     return res
 
 
+def stats_from_host(host: torch.Tensor, B: int, chunks: int, groups: int, has_r: bool, div: Optional[float], has_in: bool, div_in: float = 1e-4):
+    """The ladder's per-image statistics from a HOST copy of a Workspace.stat_buf (DepthEngine._image_stats reads it; ada_ladder_select_fwd does the same
+    arithmetic on the device and is tested against this function).  ``host``: the buffer as a flat float64 CPU tensor, laid out [B, chunks, 2] (sum |f|, sum w) of
+    the depth map | [B, groups, 2] (sum of column variances, sum of column mean squares) of the last tap | [B, rest, 2] the same of the patchified input (read only
+    with ``has_in``).  ``div``: the tap-diversity threshold, None or <= 0 for none.  Returns (r, flat, tap_div, in_div): float64 / bool [B], None for a diversity
+    that is not read; r = zeros without ``has_r``.  The pairs of a block are added in fp64.  torch's CPU sum picks its own order (several accumulators, by shape),
+    the device adds in index order: the two are the same bits whenever the sum is exact in fp64, i.e. for n fp32 terms whose magnitudes span less than
+    2^(53 - 24 - ceil(log2 n)) -- 2^26 for the eight chunks of a depth map -- and can differ by one fp64 rounding beyond that.  The
+    denominators are clamped with clamp_min, which lets a NaN through: a NaN statistic compares false with every threshold."""
+    nst, ndv = B * chunks * 2, B * groups * 2
+    st = host[:nst].view(B, chunks, 2).sum(1)
+    r = st[:, 1] / st[:, 0].clamp_min(1e-300) if has_r else torch.zeros(B, dtype=torch.float64)
+    flat = torch.zeros(B, dtype=torch.bool)
+    tap_div = in_div = None
+    if div is not None and div > 0.0:
+        dv = host[nst:nst + ndv].view(B, -1, 2).sum(1)
+        tap_div = dv[:, 0] / dv[:, 1].clamp_min(1e-300)
+        flat = tap_div < div
+    if has_in:      # every patch of the image alike: variance over patches below 1e-4 of their mean square
+        di = host[nst + ndv:].view(B, -1, 2).sum(1)
+        in_div = di[:, 0] / di[:, 1].clamp_min(1e-300)
+        flat = flat | (in_div < div_in)
+    return r, flat, tap_div, in_div
+
+
 def ladder_decide(r: torch.Tensor, flat: torch.Tensor, lad: dict, ran: int, guard: float) -> torch.Tensor:
     """THE rung rule.  ``r``: float64 [B], the per-image sensitivity read from the output of rung ``ran`` (1, 2 or 3); ``flat``: bool [B], the diversity triggers;
     ``lad``: the engine's ladder dict (keys and thresholds only: "make" / "make3" say which rungs exist, "r" / "r3" where they begin); ``guard``: the relative band

@@ -268,6 +268,12 @@ def _flat_input_rung(module, final_act, mode):
 class _EngineMixin:
     """Lazily builds / refreshes the packed weights + launch plan whenever a parameter changes."""
 
+    # False | True | "head": the precision ladder in its device mode (hip_ext.engine.DepthEngine._ladder_device) -- every rung for the whole batch, the rung
+    # of each image decided and pasted by a kernel, no host read, so that the forward can sit inside a caller's HIP-graph capture and still return what the
+    # eager ladder returns ("head": rungs 1 and 2 only).  Read at every forward; not part of the engine stamp (toggling it re-packs nothing); on a module whose engine has
+    # no ladder (precision_ladder = False, an explicit head precision) it changes nothing.  engine.device_ladder_report() reads the rungs back.
+    ladder_on_device = False
+
     def _param_tensors(self, rescan=False):
         """The parameter / buffer tensors whose (storage address, version counter) pairs stamp the packed weights.  Walking ``state_dict()`` on every
         call cost 0.7-1.0 ms for ViT-L's 425 keys -- 18 % of the single-image latency; the list is cached together with the SLOT every tensor sits in
@@ -419,9 +425,10 @@ class _EngineMixin:
         eng = self._engine()
         B = x.shape[0]
         step = eng.max_batch(x.shape[-2], x.shape[-1])
+        dev_mode = self.ladder_on_device
         if B <= step:
-            return eng.forward(x, guide, normalise)
-        outs = [eng.forward(x[i:i + step], None if guide is None else guide[i:i + step], normalise).clone() for i in range(0, B, step)]
+            return eng.forward(x, guide, normalise, on_device=dev_mode)
+        outs = [eng.forward(x[i:i + step], None if guide is None else guide[i:i + step], normalise, on_device=dev_mode).clone() for i in range(0, B, step)]
         return torch.cat(outs, dim=0)
 
 

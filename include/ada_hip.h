@@ -419,6 +419,32 @@ int ada_depth_stats_fwd(const float* in, int32_t batch, int64_t n_per_image, int
  * chunks; sum Var / sum E[t^2] ~ 0.02 marks inputs whose patch tokens are all alike (constant images), where the head's operand rounding errors add
  * coherently: the second trigger of hip_ext/engine.py's precision ladder.  No reference counterpart. */
 int ada_token_diversity_fwd(const void* tap, int64_t ld, int32_t batch, int32_t rows_per_image, int32_t dim, float* sums, void* stream);
+/* The precision ladder's decision and paste on the device: from the three statistics blocks above, still on the device, the rung of every image of a
+ * FIRST-rung run (hip_ext/ladder.py ladder_decide with ran = 1: the guard band plays no part) and the image's rows from the output of that rung.  Every
+ * pointer is a DEVICE pointer; the launch sequence (two kernels) depends on no device value, so it can be captured into a HIP graph.  No reference
+ * counterpart.
+ *   stat_sums   fp32 [batch, chunks, 2], as ada_depth_stats_fwd writes it; read only when has_r
+ *   stat_div    fp32 [batch, groups, 2] of the last tap, as ada_token_diversity_fwd writes it, or NULL (no tap-diversity trigger)
+ *   stat_in     fp32 [batch, groups_in, 2] of the patchified input, or NULL
+ *   decision    per image, in fp64, the pairs of a block added in index order starting from +0:
+ *                 r       = has_r ? S1 / clamp(S0) : 0                      (S0, S1) = the sums of stat_sums
+ *                 tap_div = V / clamp(E),  in_div likewise                  (V, E)   = the sums of stat_div / stat_in
+ *                 flat    = (stat_div && tap_div < div) || (stat_in && in_div < div_in)
+ *                 rung    = has3 && (flat || r > thr3) ? 3 : has2 && (flat || r > thr) ? 2 : 1
+ *               clamp(x) = x < 1e-300 ? 1e-300 : x, torch's clamp_min: a NaN passes through it (and then compares false everywhere: rung 1 unless
+ *               flat); `/` is the correctly rounded fp64 division.  thr / thr3 = +inf: no threshold on r.
+ *   out         fp32 [batch, n_per_image]: the first rung's output, updated IN PLACE.  Rows of rung-1 images are not touched.
+ *   src2, src3  fp32 [batch, n_per_image], the second / third rung's output for the WHOLE batch, either may be NULL; neither may alias out.  Image b's
+ *               row is copied (as bits) from src2 where rung[b] == 2 and from src3 where rung[b] == 3.  Where that source is NULL the best available
+ *               is taken -- rung 3 without src3: src2, else the row stays -- and the image counts as UNSERVED; rung[b] still names the rung it decided.
+ *               16-byte accesses wherever a row of out and its source row are congruent mod 16, word accesses in front of and behind them.
+ *   rung        int32 [batch], ratio fp64 [batch] (= r): overwritten
+ *   counts      int64 [4], ADDED to: calls, images on rung >= 2, images on rung 3, unserved images.  The caller zeroes it once.
+ * batch <= 65535. */
+int ada_ladder_select_fwd(const float* stat_sums, int32_t chunks, const float* stat_div, int32_t groups, const float* stat_in, int32_t groups_in,
+                          int32_t batch, double thr, double thr3, double div, double div_in, int32_t has2, int32_t has3, int32_t has_r,
+                          float* out, const float* src2, const float* src3, int64_t n_per_image, int32_t* rung, double* ratio, int64_t* counts,
+                          void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Image preparation and depth read-out of the raw model's infer_image / image2tensor (RAW/dpt.py:186-221), which the reference does on
