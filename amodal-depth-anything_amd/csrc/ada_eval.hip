@@ -36,7 +36,10 @@ __global__ __launch_bounds__(256) void eval_kernel(EvalArgs a) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
         if (mask && !mask[i]) continue;
         float p = pred[i] * sc + sh;
-        if (clip) p = __builtin_fminf(__builtin_fmaxf(p, a.clip_lo), a.clip_hi);
+        if (clip) {   // torch.clamp / np.clip: written as comparisons so that a NaN passes (fmaxf would return clip_lo and a broken forward report finite metrics)
+            p = p < a.clip_lo ? a.clip_lo : p;
+            p = p > a.clip_hi ? a.clip_hi : p;
+        }
         const float g = gt[i];
         const float d = p - g;
         const float lp = __logf(p), lg = __logf(g);
@@ -51,7 +54,9 @@ __global__ __launch_bounds__(256) void eval_kernel(EvalArgs a) {
         s[ADA_EVAL_ABS_REL] += (double)(__builtin_fabsf(d) / g);
         s[ADA_EVAL_SQ_REL] += (double)(d * d / g);
         s[ADA_EVAL_SQ] += (double)(d * d);
-        s[ADA_EVAL_LOG_SQ] += (double)(dl * dl);
+        // squared in double (exact): with the square rounded in fp32, sum dl^2 / n - (sum dl)^2 / n^2 of a region of equal log differences is the
+        // rounding error of one square, of either sign, and silog_rmse the square root of it
+        s[ADA_EVAL_LOG_SQ] += (double)dl * (double)dl;
         s[ADA_EVAL_LOG] += (double)dl;
         s[ADA_EVAL_LOG10_ABS] += (double)(__builtin_fabsf(dl) * 0.43429448190325176f);
         s[ADA_EVAL_D1] += ratio < T1 ? 1.0 : 0.0;

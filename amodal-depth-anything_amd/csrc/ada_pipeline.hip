@@ -7,27 +7,33 @@
 
 namespace {
 
-// one workgroup per image: per-lane running min/max, wave shuffle reduce, 16 waves combined through LDS
+// torch's amin / amax (reference infer.py:22 takes .min() / .max() of the map): a NaN on either side is the result, where fminf / fmaxf would
+// return the other operand and one NaN pixel would pass through a map normalised as if nothing had happened
+ADA_DEV float nan_min(float a, float b) { return (a < b || a != a) ? a : b; }
+ADA_DEV float nan_max(float a, float b) { return (a > b || a != a) ? a : b; }
+
+// one workgroup per image: per-lane running min/max, wave shuffle reduce, 16 waves combined through LDS.  Starts from +-inf, the identities of
+// min / max (FLT_MAX would be the "minimum" of an all-inf image); lanes without a pixel carry them through the reduction.
 __global__ __launch_bounds__(1024) void minmax_kernel(const float* __restrict__ in, long n_per_image, float* __restrict__ out) {
     __shared__ float smin[16], smax[16];
     const float* src = in + (long)blockIdx.x * n_per_image;
-    float lo = FLT_MAX, hi = -FLT_MAX;
+    float lo = __builtin_inff(), hi = -__builtin_inff();
     for (long i = threadIdx.x; i < n_per_image; i += 1024) {
         const float v = src[i];
-        lo = __builtin_fminf(lo, v);
-        hi = __builtin_fmaxf(hi, v);
+        lo = nan_min(lo, v);
+        hi = nan_max(hi, v);
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
-        lo = __builtin_fminf(lo, __shfl_xor(lo, o));
-        hi = __builtin_fmaxf(hi, __shfl_xor(hi, o));
+        lo = nan_min(lo, __shfl_xor(lo, o));
+        hi = nan_max(hi, __shfl_xor(hi, o));
     }
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { smin[w] = lo; smax[w] = hi; }
     __syncthreads();
     if (threadIdx.x == 0) {
 #pragma unroll
-        for (int i = 1; i < 16; ++i) { lo = __builtin_fminf(lo, smin[i]); hi = __builtin_fmaxf(hi, smax[i]); }
+        for (int i = 1; i < 16; ++i) { lo = nan_min(lo, smin[i]); hi = nan_max(hi, smax[i]); }
         out[2 * blockIdx.x] = lo;
         out[2 * blockIdx.x + 1] = hi;
     }
@@ -227,17 +233,19 @@ __global__ __launch_bounds__(256) void tile_blend_kernel(const float* __restrict
     if (x >= W) return;
     const int y = blockIdx.y, b = blockIdx.z;
     const float inv = 1.0f / (float)ramp;
-    float acc = 0.0f, wsum = 0.0f;
+    // The two sums and the quotient in double (a product of two floats is exact there), rounded once: summed in fp32, every tile over a pixel adds a
+    // rounding of the partial sum, and a constant field comes back two ulps off where four tiles meet.  A pixel no tile covers is 0 / 0 = NaN.
+    double acc = 0.0, wsum = 0.0;
     for (int t = 0; t < T; ++t) {
         const int ty = y - oy[t], tx = x - ox[t];
         if (ty < 0 || ty >= th || tx < 0 || tx >= tw) continue;
         const float wy = (float)min(min(ty + 1, th - ty), ramp) * inv;
         const float wx = (float)min(min(tx + 1, tw - tx), ramp) * inv;
         const float w = wy * wx;
-        acc += w * tiles[(((long)b * T + t) * th + ty) * tw + tx];
-        wsum += w;
+        acc += (double)w * (double)tiles[(((long)b * T + t) * th + ty) * tw + tx];
+        wsum += (double)w;
     }
-    out[((long)b * H + y) * W + x] = acc / wsum;
+    out[((long)b * H + y) * W + x] = (float)(acc / wsum);
 }
 
 }  // namespace

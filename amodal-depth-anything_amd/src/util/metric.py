@@ -80,7 +80,8 @@ def _from_sums(s: torch.Tensor) -> Dict[str, torch.Tensor]:
         "delta2_acc": _per_image(s, H.EVAL_D2).mean(),
         "delta3_acc": _per_image(s, H.EVAL_D3).mean(),
         "i_rmse": torch.sqrt(_per_image(s, H.EVAL_INV_SQ)).mean(),
-        "silog_rmse": torch.sqrt(torch.mean(first - second)) * 100,
+        # a variance: where every valid pixel has the same log difference the two fp64 terms differ by their last bits, of either sign (NaN stays NaN)
+        "silog_rmse": torch.sqrt(torch.mean(torch.clamp(first - second, min=0.0))) * 100,
     }
 
 

@@ -319,7 +319,8 @@ int ada_dpt_tail_fwd(const float* in, int64_t ld_in, int32_t batch, int32_t hi, 
  * align_depth_least_square (src/util/alignment.py:7-54), all from ONE pass over the maps.
  *   pred, gt   fp32 [B, n_per_image];  mask uint8 [B, n_per_image] (non-zero = valid) or NULL (all valid)
  *   scale_shift fp32 [B, 2] or NULL: p = pred * scale + shift is what gets evaluated (the aligned prediction);
- *               clip_lo < clip_hi additionally clamps p to [clip_lo, clip_hi] (dataset depth range)
+ *               clip_lo < clip_hi additionally clamps p to [clip_lo, clip_hi] (dataset depth range); like torch.clamp the clamp
+ *               passes a NaN on, so a NaN prediction under the mask makes every sum that depends on p NaN for its image
  *   sums       fp64 [B, ADA_EVAL_NSUM] (overwritten), indexed by the ADA_EVAL_* constants; p, gt must be > 0 where valid
  *               for the log / ratio / inverse terms to be meaningful (as in the reference)
  * ---------------------------------------------------------------------------------------- */
@@ -386,6 +387,7 @@ int ada_protocol_eval_fwd(const float* pred, int32_t hp, int32_t wp, const float
 /* ------------------------------------------------------------------------------------------
  * Device-side glue of the two-model pipeline of infer.py (kept in HBM instead of bouncing through numpy):
  *   ada_minmax_fwd     per-image min / max of a [B, n] fp32 map -> minmax[B, 2]          (infer.py:22)
+ *                      as torch's amin / amax: one NaN in an image makes both of its results NaN
  *   ada_normalize_fwd  norm = (d - min) / (max - min) and/or obs = norm * 2 - 1          (infer.py:22,92)
  *   ada_blend_fwd      out = mask > 0 ? amodal : base, then a 3x3 box blur (reflect-101 borders, = cv2.blur)
  *                      on the pixels whose 3x3 mask neighbourhood is mixed                (infer.py:30-44)
@@ -583,9 +585,9 @@ int ada_label_combine_fwd(const float* whole, const float* occ, const uint8_t* w
  * Tiled inference for inputs larger than the network's native 518 x 518 (the reference squashes every
  * input to 518 x 518, infer.py:17,84).  ada_tile_blend_fwd merges the per-tile predictions:
  *   tiles     fp32 [B, T, tile_h, tile_w]; tile t covers rows origin_y[t].. and columns origin_x[t].. of the full map
- *             (origin_* are DEVICE int32 [T]); every output pixel must be covered by at least one tile
+ *             (origin_* are DEVICE int32 [T]); every output pixel must be covered by at least one tile (one that is not comes out NaN)
  *   weight    separable feather min(i + 1, n - i, ramp) / ramp per axis: linear cross-fade over `ramp` pixels in overlaps
- *   out       fp32 [B, height, width] = sum_t w_t tile_t / sum_t w_t
+ *   out       fp32 [B, height, width] = sum_t w_t tile_t / sum_t w_t, both sums and the quotient in double, rounded once
  * ---------------------------------------------------------------------------------------- */
 int ada_tile_blend_fwd(const float* tiles, int32_t batch, int32_t n_tiles, int32_t tile_h, int32_t tile_w,
                        const int32_t* origin_y, const int32_t* origin_x, int32_t height, int32_t width,
