@@ -87,6 +87,36 @@ ADA_DEV op_t to_op(float v) {
 #endif
 }
 
+// ---- float4 arithmetic of the epilogues (component-wise; a * b + c contracts to one FMA per component) ----
+ADA_DEV float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+ADA_DEV float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
+ADA_DEV float4 fma4(float4 a, float4 b, float4 c) { return make_float4(a.x * b.x + c.x, a.y * b.y + c.y, a.z * b.z + c.z, a.w * b.w + c.w); }
+ADA_DEV float4 relu4(float4 v) {
+    return make_float4(__builtin_fmaxf(v.x, 0.f), __builtin_fmaxf(v.y, 0.f), __builtin_fmaxf(v.z, 0.f), __builtin_fmaxf(v.w, 0.f));
+}
+ADA_DEV opx4 pack4(float4 v) {
+    opx4 o;
+    o[0] = to_op(v.x); o[1] = to_op(v.y); o[2] = to_op(v.z); o[3] = to_op(v.w);
+    return o;
+}
+ADA_DEV opx8 cat8(opx4 a, opx4 b) { return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7); }
+
+// ---- split-precision forms of four fp32 values v (the device side of hip_ext/operands.py) ----
+//     hi  = pack4(v)                                    operand-typed, the plain form and the first segment of both split forms
+//     [hi | lo]        lo  = split_lo4(v, hi)           operand-typed round(v - hi)
+//     [hi | lo8 | hi8] lo8 = split_lo8(v, hi)           e5m2 of (v - hi) * 2^10 (ADA_F8_LO_SHIFT)
+//                      hi8 = split_hi8(v)               e5m2 of v
+// Where the words go is the caller's business: each kernel keeps its own addressing.
+ADA_DEV opx4 split_lo4(float4 v, opx4 hi) {
+    opx4 l;
+    l[0] = to_op(v.x - (float)hi[0]); l[1] = to_op(v.y - (float)hi[1]); l[2] = to_op(v.z - (float)hi[2]); l[3] = to_op(v.w - (float)hi[3]);
+    return l;
+}
+ADA_DEV uint32_t split_lo8(float4 v, opx4 hi) {
+    return bf8x4((v.x - (float)hi[0]) * ADA_F8_LO_SHIFT, (v.y - (float)hi[1]) * ADA_F8_LO_SHIFT, (v.z - (float)hi[2]) * ADA_F8_LO_SHIFT, (v.w - (float)hi[3]) * ADA_F8_LO_SHIFT);
+}
+ADA_DEV uint32_t split_hi8(float4 v) { return bf8x4(v.x, v.y, v.z, v.w); }
+
 // unsigned division by a runtime constant through its float reciprocal; exact for n < 2^24
 struct FastDiv {
     uint32_t d;

@@ -9,36 +9,25 @@
 
 namespace {
 
-// operand-typed float4 store; split_seg > 0 writes [hi | lo] column segments (split precision, see ada_igemm_args.split_seg), < 0 the fp8 form
-ADA_DEV void store_op4_split(op_t* row, int c, float4 r, int split_seg) {
-    opx4 o;
-    o[0] = to_op(r.x); o[1] = to_op(r.y); o[2] = to_op(r.z); o[3] = to_op(r.w);
-    ((opx4*)row)[c] = o;
-    if (split_seg > 0) {
-        opx4 l;
-        l[0] = to_op(r.x - (float)o[0]); l[1] = to_op(r.y - (float)o[1]); l[2] = to_op(r.z - (float)o[2]); l[3] = to_op(r.w - (float)o[3]);
-        ((opx4*)(row + split_seg))[c] = l;
-    } else if (split_seg < 0) {   // [hi | lo8 | hi8]: e5m2 bytes behind the hi segment (ada_igemm_args.f8_from)
-        uint32_t* b = (uint32_t*)(row - split_seg);
-        b[c] = bf8x4((r.x - (float)o[0]) * ADA_F8_LO_SHIFT, (r.y - (float)o[1]) * ADA_F8_LO_SHIFT, (r.z - (float)o[2]) * ADA_F8_LO_SHIFT, (r.w - (float)o[3]) * ADA_F8_LO_SHIFT);
-        b[c + (-split_seg) / 4] = bf8x4(r.x, r.y, r.z, r.w);
-    }
-}
-
-// The resize kernels' outputs are written once and read by a later launch: non-temporal stores keep them
+// operand-typed float4 store of chunk c of a row; split_seg > 0 writes [hi | lo] column segments (split precision, see ada_igemm_args.split_seg),
+// < 0 the fp8 form [hi | lo8 | hi8]: e5m2 bytes behind the hi segment (ada_igemm_args.f8_from).  The forms' values: ada_common.h.
+// NT: the resize kernels' outputs are written once and read by a later launch: non-temporal stores keep them
 // from displacing the input rows the neighbouring workgroups still read (profiles/r03_o, +0.3 % end to end).
-ADA_DEV void store_op4_bil(op_t* row, int c, float4 r, int split_seg) {
-    opx4 o;
-    o[0] = to_op(r.x); o[1] = to_op(r.y); o[2] = to_op(r.z); o[3] = to_op(r.w);
-    __builtin_nontemporal_store(o, ((opx4*)row) + c);
+template <bool NT>
+ADA_DEV void st_op4(opx4 o, opx4* dst) {
+    if constexpr (NT) __builtin_nontemporal_store(o, dst);
+    else *dst = o;
+}
+template <bool NT>
+ADA_DEV void store_op4_split(op_t* row, int c, float4 r, int split_seg) {
+    const opx4 o = pack4(r);
+    st_op4<NT>(o, ((opx4*)row) + c);
     if (split_seg > 0) {
-        opx4 l;
-        l[0] = to_op(r.x - (float)o[0]); l[1] = to_op(r.y - (float)o[1]); l[2] = to_op(r.z - (float)o[2]); l[3] = to_op(r.w - (float)o[3]);
-        __builtin_nontemporal_store(l, ((opx4*)(row + split_seg)) + c);
+        st_op4<NT>(split_lo4(r, o), ((opx4*)(row + split_seg)) + c);
     } else if (split_seg < 0) {
         uint32_t* b = (uint32_t*)(row - split_seg);
-        b[c] = bf8x4((r.x - (float)o[0]) * ADA_F8_LO_SHIFT, (r.y - (float)o[1]) * ADA_F8_LO_SHIFT, (r.z - (float)o[2]) * ADA_F8_LO_SHIFT, (r.w - (float)o[3]) * ADA_F8_LO_SHIFT);
-        b[c + (-split_seg) / 4] = bf8x4(r.x, r.y, r.z, r.w);
+        b[c] = split_lo8(r, o);
+        b[c + (-split_seg) / 4] = split_hi8(r);
     }
 }
 ADA_DEV void store_f32_bil(float* ptr, float4 r) {
@@ -201,7 +190,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs p) {
                 y.x = __builtin_fmaxf(y.x, 0.f); y.y = __builtin_fmaxf(y.y, 0.f);
                 y.z = __builtin_fmaxf(y.z, 0.f); y.w = __builtin_fmaxf(y.w, 0.f);
             }
-            if (p.out_op) store_op4_split(p.out_op + orow * p.ld_op, c, y, p.split_seg);
+            if (p.out_op) store_op4_split<false>(p.out_op + orow * p.ld_op, c, y, p.split_seg);
         }
     }
     if (p.out2) {
@@ -221,7 +210,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnArgs p) {
                 y.y = (v[i].y - mean) * rstd * w.y + bb.y;
                 y.z = (v[i].z - mean) * rstd * w.z + bb.z;
                 y.w = (v[i].w - mean) * rstd * w.w + bb.w;
-                store_op4_split(dst, c, y, p.split_seg2);
+                store_op4_split<false>(dst, c, y, p.split_seg2);
             }
         }
     }
@@ -337,7 +326,7 @@ __global__ __launch_bounds__(256) void bilinear_kernel(BilinearArgs p) {
             r.x = __builtin_fmaxf(r.x, 0.f); r.y = __builtin_fmaxf(r.y, 0.f);
             r.z = __builtin_fmaxf(r.z, 0.f); r.w = __builtin_fmaxf(r.w, 0.f);
         }
-        store_op4_bil(p.out_op + orow * p.ld_op, c, r, p.split_seg);
+        store_op4_split<true>(p.out_op + orow * p.ld_op, c, r, p.split_seg);
     }
 }
 
@@ -418,7 +407,7 @@ __global__ __launch_bounds__(256) void bilinear_tiled_kernel(BilinearArgs p, int
                 r.x = __builtin_fmaxf(r.x, 0.f); r.y = __builtin_fmaxf(r.y, 0.f);
                 r.z = __builtin_fmaxf(r.z, 0.f); r.w = __builtin_fmaxf(r.w, 0.f);
             }
-            store_op4_bil(p.out_op + orow * p.ld_op, c, r, p.split_seg);
+            store_op4_split<true>(p.out_op + orow * p.ld_op, c, r, p.split_seg);
         }
     }
 }

@@ -35,28 +35,6 @@ namespace {
 
 enum { EPI_STD = 0, EPI_GELU = 1, EPI_SHUFFLE = 2, EPI_SWIGLU = 3, EPI_TAIL = 4 };
 
-// Non-temporal hints on the streaming traffic of the epilogues (round 3 A/B) -- bit 0: the fp32 residual loads, bit 1: the fp32 stores (both
-// neutral end to end: off), bit 2: the 16-byte operand-typed stores (+1.0 % end to end: ON).
-#ifndef ADA_EPI_NT
-#define ADA_EPI_NT 4
-#endif
-ADA_DEV float4 ld_res4(const float* ptr) {
-#if ADA_EPI_NT & 1
-    const f32x4 v = __builtin_nontemporal_load((const f32x4*)ptr);
-    return make_float4(v[0], v[1], v[2], v[3]);
-#else
-    return *(const float4*)ptr;
-#endif
-}
-ADA_DEV void st_f32x4(float* ptr, float4 v) {
-#if ADA_EPI_NT & 2
-    const f32x4 t = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(t, (f32x4*)ptr);
-#else
-    *(float4*)ptr = v;
-#endif
-}
-
 struct IgemmDev {
     int M, N, K, a_mode;
     const op_t* A;
@@ -95,7 +73,6 @@ struct IgemmDev {
     float tail_b;
     int tail_act;
     int tiles_m, tiles_n;
-    int cps;  // k-steps per conv tap = lda / 64
     int variant;  // main-loop variant for A/B runs (ada_debug_set_variant)
     int group_n;  // tile order: N-tiles are walked in column groups of this width (== tiles_n: plain row-major)
     unsigned long long* dbg;  // optional per-block timestamps (ada_debug_set_timestamps)
@@ -132,20 +109,57 @@ ADA_DEV void gelu_erf4(float4& v) {
 // SiLU of the SwiGLU gate (reference swiglu_ffn.py:31): t * sigmoid(t), the division as one v_rcp (1 ulp) instead of the IEEE sequence
 ADA_DEV float silu(float t) { return t * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896340736f * t)); }
 
-// GEMM row -> row of an output buffer
-ADA_DEV long map_row(const IgemmDev& p, int map, uint32_t m) {
-    if (map == ADA_MAP_PLAIN) return (long)m;
-    if (map == ADA_MAP_TOKEN) {
-        uint32_t b, r;
-        fast_divmod(m, p.dMapHW, b, r);
-        return (long)m + b + 1;
+// ---- epilogue pieces shared by the paths of igemm_kernel ----
+
+// Per-lane column constants: bias (default 0) and gamma (default 1) of the NV float4 column groups from column n on.  Edge tiles pass ok0 / ok1 =
+// "group 0 / 1 lies inside N"; a group that does not keeps its defaults.
+template <int NV>
+struct ColConst {
+    float4 b[NV], g[NV];
+};
+template <int NV>
+ADA_DEV ColConst<NV> col_const(const IgemmDev& p, int n, bool ok0 = true, bool ok1 = true) {
+    static_assert(NV == 1 || NV == 2, "4 or 8 columns per lane");
+    ColConst<NV> c;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        c.b[j] = make_float4(0, 0, 0, 0);
+        c.g[j] = make_float4(1, 1, 1, 1);
     }
-    // PAD: interior of [B, map_h+2, map_w+2]
-    uint32_t b, rem, y, x;
-    fast_divmod(m, p.dMapHW, b, rem);
-    fast_divmod(rem, p.dMapW, y, x);
-    return ((long)b * (p.map_h + 2) + (y + 1)) * (p.map_w + 2) + (x + 1);
+    if (p.flags & ADA_EP_BIAS) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+            if (j == 0 ? ok0 : ok1) c.b[j] = *(const float4*)(p.bias + n + 4 * j);
+    }
+    if (p.flags & ADA_EP_GAMMA) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j)
+            if (j == 0 ? ok0 : ok1) c.g[j] = *(const float4*)(p.gamma + n + 4 * j);
+    }
+    return c;
 }
+
+// The value chain of the STD / GELU / SHUFFLE epilogues on NV float4 column groups: accumulator + bias -> GELU -> * gamma (+ residual), stage by
+// stage over the groups.  RES: the path carries a residual operand r (zeros when the launch has none) and folds it in as fma(v + b, g, r); without
+// one it is (v + b) * g, the multiply skipped where the caller knows gamma is absent (scale = false).  ReLU comes after, per copy (relu4_if): the
+// fp32 and the operand-typed copy of a value have separate flags.
+template <int EPI, bool RES, int NV>
+ADA_DEV void epi_value(float4 (&v)[NV], const ColConst<NV>& c, const float4* r, bool scale = true) {
+#pragma unroll
+    for (int j = 0; j < NV; ++j) v[j] = add4(v[j], c.b[j]);
+    if constexpr (EPI == EPI_GELU) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) gelu_erf4(v[j]);
+    }
+    if constexpr (RES) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) v[j] = fma4(v[j], c.g[j], r[j]);
+    } else if (scale) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) v[j] = mul4(v[j], c.g[j]);
+    }
+}
+ADA_DEV float4 relu4_if(float4 v, bool on) { return on ? relu4(v) : v; }
 
 // Walks GEMM rows m, m+step, m+2*step ... through the interior of a zero-bordered [B, map_h+2, map_w+2] grid without a
 // division per row (valid for step <= map_w).
@@ -176,69 +190,78 @@ ADA_DEV void pad_step(const IgemmDev& p, PadWalk& w, int step) {
     }
 }
 
-ADA_DEV opx4 pack4(float4 v) {
-    opx4 o;
-    o[0] = to_op(v.x); o[1] = to_op(v.y); o[2] = to_op(v.z); o[3] = to_op(v.w);
-    return o;
+// GEMM row -> row of an output buffer
+ADA_DEV long map_row(const IgemmDev& p, int map, uint32_t m) {
+    if (map == ADA_MAP_PLAIN) return (long)m;
+    if (map == ADA_MAP_TOKEN) {
+        uint32_t b, r;
+        fast_divmod(m, p.dMapHW, b, r);
+        return (long)m + b + 1;
+    }
+    return pad_start(p, m).prow;   // PAD: interior of [B, map_h+2, map_w+2]
 }
 
-// Operand-typed stores.  With split_seg > 0 the value is written in split precision, hi = round(v) at column n, lo = round(v - hi) at
-// n + seg: a following contraction over the THREE k segments (hi, lo, hi) -- the third re-reads the first, ada_igemm_args.a_dup_seg --
-// against weights packed [w_hi | w_hi | w_lo] evaluates x_hi w_hi + x_lo w_hi + x_hi w_lo, i.e. the product to ~fp32 accuracy on the fp16
-// matrix cores (used for selected contractions of the DPT head and the patch embedding).
+// EPI_SHUFFLE (pixel shuffle by s): GEMM column n = (i * s + j) * shuffle_c + co is channel co of sub-pixel (i, j); GEMM row m = pixel (b, y, x)
+// of the coarse map_h x map_w grid lands on row (s y + i, s x + j) of the zero-bordered fine grid
+struct ShufflePhase {
+    uint32_t i, j, co;
+};
+ADA_DEV ShufflePhase shuffle_phase(const IgemmDev& p, uint32_t n) {
+    ShufflePhase s;
+    uint32_t ij;
+    fast_divmod(n, p.dShC, ij, s.co);
+    fast_divmod(ij, p.dShS, s.i, s.j);
+    return s;
+}
+ADA_DEV long shuffle_row(const IgemmDev& p, uint32_t m, ShufflePhase s) {
+    uint32_t sb, rem, sy, sx;
+    fast_divmod(m, p.dMapHW, sb, rem);
+    fast_divmod(rem, p.dMapW, sy, sx);
+    return ((long)sb * (p.shuffle_s * p.map_h + 2) + (p.shuffle_s * sy + s.i + 1)) * (p.shuffle_s * p.map_w + 2) + (p.shuffle_s * sx + s.j + 1);
+}
+
+// Operand-typed stores: address arithmetic around the split forms of ada_common.h.  With split_seg > 0 the value is written in split precision,
+// hi at column n, lo at n + seg: a following contraction over the THREE k segments (hi, lo, hi) -- the third re-reads the first,
+// ada_igemm_args.a_dup_seg -- against weights packed [w_hi | w_hi | w_lo] evaluates x_hi w_hi + x_lo w_hi + x_hi w_lo, i.e. the product to
+// ~fp32 accuracy on the fp16 matrix cores (used for selected contractions of the DPT head and the patch embedding).
 // (col = dst's column inside its row: the byte segments of the [hi | lo8 | hi8] form start at row + seg, one byte per column)
+// F8OK = false leaves the fp8 form out of a call site that never sees it.
 template <bool F8OK = true>
 ADA_DEV void store_op4(const IgemmDev& p, op_t* dst, int col, float4 v) {
     const opx4 h = pack4(v);
     *(opx4*)dst = h;
     if (p.split_seg > 0) {
-        float4 r;
-        r.x = v.x - (float)h[0]; r.y = v.y - (float)h[1]; r.z = v.z - (float)h[2]; r.w = v.w - (float)h[3];
         if (F8OK && p.split_f8) {
             char* b = (char*)dst + (2 * p.split_seg - col);        // = (char*)(row + seg) + col
-            *(uint32_t*)b = bf8x4(r.x * ADA_F8_LO_SHIFT, r.y * ADA_F8_LO_SHIFT, r.z * ADA_F8_LO_SHIFT, r.w * ADA_F8_LO_SHIFT);
-            *(uint32_t*)(b + p.split_seg) = bf8x4(v.x, v.y, v.z, v.w);
+            *(uint32_t*)b = split_lo8(v, h);
+            *(uint32_t*)(b + p.split_seg) = split_hi8(v);
         } else {
-            *(opx4*)(dst + p.split_seg) = pack4(r);
+            *(opx4*)(dst + p.split_seg) = split_lo4(v, h);
         }
     }
 }
 template <bool F8OK = true>
 ADA_DEV void store_op8(const IgemmDev& p, op_t* dst, int col, float4 v0, float4 v1) {
-    const opx4 lo = pack4(v0), hi4 = pack4(v1);
-    opx8 o;
-    o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = lo[3];
-    o[4] = hi4[0]; o[5] = hi4[1]; o[6] = hi4[2]; o[7] = hi4[3];
+    const opx4 h0 = pack4(v0), h1 = pack4(v1);
     // The 16-byte operand-typed stores are non-temporal: the output of a linear layer / conv is written once here and read by the NEXT
     // kernel; streamed past the caches it does not push this GEMM's weight slabs and A panels out of L2 (fc1 + GELU 427 -> 390 us per
-    // launch, +1.0 % end to end: profiles/r03_o_nontemporal_stores_ab.txt).  Compile-time on purpose: behind a runtime branch the
+    // launch, +1.0 % end to end: profiles/r03_o_nontemporal_stores_ab.txt).  Unconditional on purpose: behind a runtime branch the
     // optimiser merges the two stores and drops the hint (checked in the .s).  The same hint on the 8-byte stores, on the attention output,
     // on LayerNorm / bilinear outputs and on the fp32 residual traffic measured neutral or negative.
-#if ADA_EPI_NT & 4
-    __builtin_nontemporal_store(o, (opx8*)dst);
-#else
-    *(opx8*)dst = o;
-#endif
+    __builtin_nontemporal_store(cat8(h0, h1), (opx8*)dst);
     if (p.split_seg > 0) {
-        float4 r0, r1;
-        r0.x = v0.x - (float)lo[0]; r0.y = v0.y - (float)lo[1]; r0.z = v0.z - (float)lo[2]; r0.w = v0.w - (float)lo[3];
-        r1.x = v1.x - (float)hi4[0]; r1.y = v1.y - (float)hi4[1]; r1.z = v1.z - (float)hi4[2]; r1.w = v1.w - (float)hi4[3];
         if (F8OK && p.split_f8) {
             char* b8 = (char*)dst + (2 * p.split_seg - col);       // = (char*)(row + seg) + col
             u32x2 l8, h8;
-            l8[0] = bf8x4(r0.x * ADA_F8_LO_SHIFT, r0.y * ADA_F8_LO_SHIFT, r0.z * ADA_F8_LO_SHIFT, r0.w * ADA_F8_LO_SHIFT);
-            l8[1] = bf8x4(r1.x * ADA_F8_LO_SHIFT, r1.y * ADA_F8_LO_SHIFT, r1.z * ADA_F8_LO_SHIFT, r1.w * ADA_F8_LO_SHIFT);
-            h8[0] = bf8x4(v0.x, v0.y, v0.z, v0.w);
-            h8[1] = bf8x4(v1.x, v1.y, v1.z, v1.w);
+            l8[0] = split_lo8(v0, h0);
+            l8[1] = split_lo8(v1, h1);
+            h8[0] = split_hi8(v0);
+            h8[1] = split_hi8(v1);
             *(u32x2*)b8 = l8;
             *(u32x2*)(b8 + p.split_seg) = h8;
-            return;
+        } else {
+            *(opx8*)(dst + p.split_seg) = cat8(split_lo4(v0, h0), split_lo4(v1, h1));
         }
-        const opx4 a = pack4(r0), b = pack4(r1);
-        opx8 l;
-        l[0] = a[0]; l[1] = a[1]; l[2] = a[2]; l[3] = a[3];
-        l[4] = b[0]; l[5] = b[1]; l[6] = b[2]; l[7] = b[3];
-        *(opx8*)(dst + p.split_seg) = l;
     }
 }
 
@@ -348,18 +371,6 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4 && 
     const int sps = p.a_dup_seg / BK;                                   // k-steps per segment (0: plain operand)
     const int wrap = sps > 0 ? 2 * sps : p.a_wrap / BK;                 // PLAIN: k-step at which the A walk starts over (0: never)
     const int cps = sps > 0 ? 3 * sps : (int)(p.lda / BK);              // k-steps per conv tap
-    auto slab_offsets = [&](int kt, long& aoff, long& boff) {
-        if (p.a_mode == ADA_A_PLAIN) {
-            aoff = (long)((wrap > 0 && kt >= wrap) ? kt - wrap : kt) * BK;
-        } else {
-            const int tap = kt / cps;
-            int kc = kt - tap * cps;
-            if (sps > 0 && kc >= 2 * sps) kc -= 2 * sps;
-            const int dy = tap / 3, dx = tap - dy * 3;
-            aoff = ((long)dy * p.Wp + dx) * p.lda + (long)kc * BK;
-        }
-        boff = (long)kt * BK;
-    };
     // issue the global->LDS copies of part `part` (of NSUB) of a stage; part < 0 issues everything
     auto stage_part = [&](int buf, long aoff, long boff, int part) {
         char* sa = smem + buf * STAGE_BYTES + wave * 1024;
@@ -413,36 +424,6 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4 && 
             if ((mask >> t) & 1u) taps_packed |= (unsigned long long)t << (4 * ntaps++);
     }
     const int nk = p.a_mode == ADA_A_PLAIN ? p.K / BK : ntaps * cps;
-    if constexpr (PIPE4) {
-        // everything between here and the epilogue's first dump() is the generated asm: fragments in v[0:127], accumulators in a[0:255]
-        const int l15 = lane & 15, q4 = lane >> 4;
-        const unsigned lds0 = (unsigned)(size_t)smem;
-        const unsigned coff0 = (unsigned)((q4 ^ ((l15 >> 1) & 7)) * 16);
-        const unsigned abase = lds0 + (unsigned)((wm * 128 + l15) * RB) + coff0;
-        const unsigned bbase = lds0 + (unsigned)(A_BYTES + (wn * 128 + l15) * RB) + coff0;
-        const unsigned m0s0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + (unsigned)wave * 1024u));
-        constexpr unsigned OOB = 0x7fffffffu;     // a scalar offset beyond num_records: the copy zero-fills without fetching
-        long a0o, b0o, a1o = 0, b1o = 0, a2o = 0, b2o = 0;
-        slab_offsets(0, a0o, b0o);
-        if (nk > 1) slab_offsets(1, a1o, b1o);
-        if (nk > 2) slab_offsets(2, a2o, b2o);
-        unsigned period = 0x7fffffffu, cnt = 0, jump = 0;
-        if (p.a_mode != ADA_A_PLAIN) {   // 3x3 conv: consecutive k-tiles of an input row (three taps) are contiguous; every 3 * cps k-tiles the
-            period = (unsigned)(3 * cps);   // A window moves down one padded input row
-            cnt = 2u % period;
-            jump = (unsigned)(((long)(p.Wp - 3) * p.lda) * 2);
-        }
-        // the asm needs the two buffer resources in SGPRs: rebuild them from readfirstlane'd pointer halves so that their uniformity is
-        // provable (the tile bases come out of float-reciprocal divisions, i.e. VALU registers -- cdna_hip_programming.md T20)
-        auto uniform_rsrc = [](const void* ptr) {
-            const unsigned long long v = (unsigned long long)ptr;
-            const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-            return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, 0x7fffffff, 0x20000);
-        };
-        const __amdgpu_buffer_rsrc_t a_rs = uniform_rsrc(a_tile), b_rs = uniform_rsrc(b_tile);
-        pipe4_main_loop(a_rs, b_rs, a_off, b_off, abase, bbase, m0s0, (unsigned)(a0o * 2), nk > 1 ? (unsigned)(a1o * 2) : OOB, nk > 1 ? 128u : OOB,
-                        (unsigned)(a2o * 2), (unsigned)nk, period, cnt, jump);
-    } else {
     // Offsets of the next slab to stage.  Plain operands walk k-step j directly; a 3x3 conv walks (active tap, k-step inside the tap) with two
     // scalar counters (no division per k-step), the taps taken from taps_packed.  The walk state is passed and returned BY VALUE: captured by
     // reference it has its address taken, and the "memory" clobbers of the loop's waits then pin it to scratch (12 bytes, reloaded every k-step).
@@ -465,6 +446,38 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4 && 
         }
         return w;
     };
+    if constexpr (PIPE4) {
+        // everything between here and the epilogue's first dump() is the generated asm: fragments in v[0:127], accumulators in a[0:255]
+        const int l15 = lane & 15, q4 = lane >> 4;
+        const unsigned lds0 = (unsigned)(size_t)smem;
+        const unsigned coff0 = (unsigned)((q4 ^ ((l15 >> 1) & 7)) * 16);
+        const unsigned abase = lds0 + (unsigned)((wm * 128 + l15) * RB) + coff0;
+        const unsigned bbase = lds0 + (unsigned)(A_BYTES + (wn * 128 + l15) * RB) + coff0;
+        const unsigned m0s0 = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + (unsigned)wave * 1024u));
+        constexpr unsigned OOB = 0x7fffffffu;     // a scalar offset beyond num_records: the copy zero-fills without fetching
+        // the generated loop is primed with the A offsets of the first three k-steps of the walk and advances them itself (period / jump below: it
+        // is launched for unsplit, unwrapped, unmasked walks only -- use_pipe4 -- whose W offset is 128 bytes per k-step: boff is not used here)
+        long a0o, a1o = 0, a2o = 0, boff;
+        Walk w3 = next_offsets(Walk{0, 0, 0}, a0o, boff);
+        if (nk > 1) w3 = next_offsets(w3, a1o, boff);
+        if (nk > 2) w3 = next_offsets(w3, a2o, boff);
+        unsigned period = 0x7fffffffu, cnt = 0, jump = 0;
+        if (p.a_mode != ADA_A_PLAIN) {   // 3x3 conv: consecutive k-tiles of an input row (three taps) are contiguous; every 3 * cps k-tiles the
+            period = (unsigned)(3 * cps);   // A window moves down one padded input row
+            cnt = 2u % period;
+            jump = (unsigned)(((long)(p.Wp - 3) * p.lda) * 2);
+        }
+        // the asm needs the two buffer resources in SGPRs: rebuild them from readfirstlane'd pointer halves so that their uniformity is
+        // provable (the tile bases come out of float-reciprocal divisions, i.e. VALU registers -- cdna_hip_programming.md T20)
+        auto uniform_rsrc = [](const void* ptr) {
+            const unsigned long long v = (unsigned long long)ptr;
+            const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+            return __builtin_amdgcn_make_buffer_rsrc((void*)(((unsigned long long)hi << 32) | lo), 0, 0x7fffffff, 0x20000);
+        };
+        const __amdgpu_buffer_rsrc_t a_rs = uniform_rsrc(a_tile), b_rs = uniform_rsrc(b_tile);
+        pipe4_main_loop(a_rs, b_rs, a_off, b_off, abase, bbase, m0s0, (unsigned)(a0o * 2), nk > 1 ? (unsigned)(a1o * 2) : OOB, nk > 1 ? 128u : OOB,
+                        (unsigned)(a2o * 2), (unsigned)nk, period, cnt, jump);
+    } else {
     Walk walk{0, 0, 0};
     {
         long aoff, boff;
@@ -629,6 +642,54 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4 && 
     };
     static_assert((GJ - 1) * 32 + 16 + 3 * SW < 256, "ds_write2_b32 offsets are 8 bits");
 
+    // The 4-column paths (fp32 output and / or residual): every pass q = g * TI + i transposes one 32-row block of column group g and each lane
+    // handles rows k * RPI4 + rsub, k < NKI, of it.  res_passes is their common skeleton: the residual rows of a pass are loaded together, on
+    // 8-wave tiles one pass AHEAD of their use (the registers are there; with 2-3 co-resident workgroups the neighbours' MFMAs cover the
+    // latency instead and the 32 extra VGPRs would spill), so their HBM latency hides behind the LDS transpose.  The caller supplies
+    //   res_addr(q, k)   address of the lane's residual float4 of row k of pass q (must be loadable whenever the launch has a residual),
+    //   begin(g, i)      the pass's state (column constants, row bases), built before the loads are issued,
+    //   row(st, k, r)    what to do with row k, r = its residual (zeros without one).
+    // res_passes and its callbacks capture BY VALUE, like next_offsets: captured by reference through two levels of closures, `p` keeps its address
+    // taken, and the "memory" clobbers of dump() then make every pass re-read the kernel arguments it uses (the row-map divisors alone 50 times in a
+    // 128x64 kernel: +7 % instructions in the .s of every STD / GELU / SHUFFLE kernel).
+    constexpr int CG4 = GW / 4, RPI4 = 64 / CG4, NKI = 32 / RPI4, NPASS = NG * TI;
+    auto res_passes = [=](auto res_addr, auto begin, auto row) __attribute__((always_inline)) {
+        constexpr bool AHEAD = (NWAVES == 8 && TJ <= 2) || PIPE4;
+        const bool has_res = (flags & ADA_EP_RESIDUAL) != 0;
+        float4 rcur[NKI], rnext[AHEAD ? NKI : 1];
+#pragma unroll
+        for (int k = 0; k < NKI; ++k) rcur[k] = make_float4(0, 0, 0, 0);
+        if (AHEAD && has_res) {
+#pragma unroll
+            for (int k = 0; k < NKI; ++k) rcur[k] = *(const float4*)res_addr(0, k);
+        }
+#pragma unroll
+        for (int q = 0; q < NPASS; ++q) {
+            const int g = q / TI, i = q - g * TI;
+            auto st = begin(g, i);
+            if constexpr (AHEAD) {
+                if (has_res && q + 1 < NPASS) {
+#pragma unroll
+                    for (int k = 0; k < NKI; ++k) rnext[k] = *(const float4*)res_addr(q + 1, k);
+                }
+            } else {
+                if (has_res) {
+#pragma unroll
+                    for (int k = 0; k < NKI; ++k) rcur[k] = *(const float4*)res_addr(q, k);
+                }
+            }
+            dump(i, g);
+#pragma unroll
+            for (int k = 0; k < NKI; ++k) row(st, k, rcur[k]);
+            if constexpr (AHEAD) {
+                if (has_res) {
+#pragma unroll
+                    for (int k = 0; k < NKI; ++k) rcur[k] = rnext[k];
+                }
+            }
+        }
+    };
+
     if constexpr (EPI == EPI_SWIGLU) {
         // packer interleaved the w12 rows in 32-wide groups: columns [0,32) of a 64-column group = x1, [32,64) = x2
         static_assert(GW == 64 || EPI != EPI_SWIGLU, "SwiGLU needs 64-column groups");
@@ -707,7 +768,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4 && 
         //      the head: no bounds checks, no per-row division, row pointers advance by constant strides / a PadWalk.  The general code below spends most of its issue slots on exactly that
         //      bookkeeping: 10.7 k cycles per 256x256 tile for fp16 output, 35 k for the fp32 residual update, against 4-8 k
         //      for this path (profiles/r01_g_gemm_tile_anatomy.txt) -- the epilogue is VALU-issue-bound, not memory-bound.
-        const bool has_bias = (flags & ADA_EP_BIAS) != 0, has_gamma = (flags & ADA_EP_GAMMA) != 0;
+        const bool has_gamma = (flags & ADA_EP_GAMMA) != 0;
         if (!p.out_f32 && !(flags & ADA_EP_RESIDUAL)) {
             constexpr int CG = GW / 8, RPI = 64 / CG;
             // Lane -> (slab row rsub, column group cg).  The slab reads are ds_read_b128, serviced in the lane groups {0-3, 12-15, 20-27},
@@ -720,9 +781,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4 && 
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
                 const int n = nwave + g * GW + 8 * cg;
-                float4 b0 = make_float4(0, 0, 0, 0), b1 = b0, g0 = make_float4(1, 1, 1, 1), g1 = g0;
-                if (has_bias) { b0 = *(const float4*)(p.bias + n); b1 = *(const float4*)(p.bias + n + 4); }
-                if (has_gamma) { g0 = *(const float4*)(p.gamma + n); g1 = *(const float4*)(p.gamma + n + 4); }
+                const ColConst<2> c = col_const<2>(p, n);
                 op_t* dst = p.out_op + (long)(mbase + rsub) * ld + n;
                 const bool pad = p.map_op == ADA_MAP_PAD;
 #pragma unroll
@@ -733,114 +792,61 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4 && 
 #pragma unroll
                     for (int k = 0; k < 32 / RPI; ++k) {
                         const int row = k * RPI + rsub;
-                        float4 v0 = *(const float4*)(slab + row * SW + 8 * cg);
-                        float4 v1 = *(const float4*)(slab + row * SW + 8 * cg + 4);
-                        v0.x += b0.x; v0.y += b0.y; v0.z += b0.z; v0.w += b0.w;
-                        v1.x += b1.x; v1.y += b1.y; v1.z += b1.z; v1.w += b1.w;
-                        if constexpr (EPI == EPI_GELU) {
-                            gelu_erf4(v0);
-                            gelu_erf4(v1);
-                        }
-                        if (has_gamma) {
-                            v0.x *= g0.x; v0.y *= g0.y; v0.z *= g0.z; v0.w *= g0.w;
-                            v1.x *= g1.x; v1.y *= g1.y; v1.z *= g1.z; v1.w *= g1.w;
-                        }
+                        float4 v[2] = {*(const float4*)(slab + row * SW + 8 * cg), *(const float4*)(slab + row * SW + 8 * cg + 4)};
+                        epi_value<EPI, false>(v, c, nullptr, has_gamma);
                         if (relu) {
-                            v0.x = __builtin_fmaxf(v0.x, 0.f); v0.y = __builtin_fmaxf(v0.y, 0.f); v0.z = __builtin_fmaxf(v0.z, 0.f); v0.w = __builtin_fmaxf(v0.w, 0.f);
-                            v1.x = __builtin_fmaxf(v1.x, 0.f); v1.y = __builtin_fmaxf(v1.y, 0.f); v1.z = __builtin_fmaxf(v1.z, 0.f); v1.w = __builtin_fmaxf(v1.w, 0.f);
+                            v[0] = relu4(v[0]);
+                            v[1] = relu4(v[1]);
                         }
                         if (pad) {
-                            store_op8(p, p.out_op + walk.prow * ld + n, n, v0, v1);
+                            store_op8(p, p.out_op + walk.prow * ld + n, n, v[0], v[1]);
                             pad_step(p, walk, RPI);
                         } else {
-                            store_op8(p, dst + (long)(i * 32 + k * RPI) * ld, n, v0, v1);
+                            store_op8(p, dst + (long)(i * 32 + k * RPI) * ld, n, v[0], v[1]);
                         }
                     }
                 }
             }
         } else {
-            constexpr int CG = GW / 4, RPI = 64 / CG, NKI = 32 / RPI, NPASS = NG * TI;
-            const int rsub = lane / CG, cg = CG == 16 ? ((lane - rsub) & 15) : lane % CG;   // column group rotated by the row: see above
-            const bool has_res = (flags & ADA_EP_RESIDUAL) != 0;
+            const int rsub = lane / CG4, cg = CG4 == 16 ? ((lane - rsub) & 15) : lane % CG4;   // column group rotated by the row: see above
             const bool relu_f = (flags & ADA_EP_RELU_F32) != 0, relu_o = (flags & ADA_EP_RELU_OP) != 0;
             const long ldr = p.ldr, ldf = p.ldo_f32, ldo = p.ldo_op;
-            auto rptr = [&](int q) -> const float* {
-                const int g = q / TI, i = q - g * TI;
-                return p.res + (long)(mbase + i * 32 + rsub) * ldr + (nwave + g * GW + 4 * cg);
-            };
-            // residual rows of the next 32-row pass are requested before this pass is transposed (8-wave tiles: the registers
-            // are there; with co-resident workgroups the neighbours' MFMAs cover the latency instead)
-            constexpr bool AHEAD = (NWAVES == 8 && TJ <= 2) || PIPE4;
-            float4 rcur[NKI], rnext[AHEAD ? NKI : 1];
-#pragma unroll
-            for (int k = 0; k < NKI; ++k) rcur[k] = make_float4(0, 0, 0, 0);
-            if (AHEAD && has_res) {
-                const float* r0 = rptr(0);
-#pragma unroll
-                for (int k = 0; k < NKI; ++k) rcur[k] = ld_res4(r0 + (long)(k * RPI) * ldr);
-            }
-#pragma unroll
-            for (int q = 0; q < NPASS; ++q) {
-                const int g = q / TI, i = q - g * TI;
-                const int n = nwave + g * GW + 4 * cg;
-                float4 bias4 = make_float4(0, 0, 0, 0), gamma4 = make_float4(1, 1, 1, 1);
-                if (has_bias) bias4 = *(const float4*)(p.bias + n);
-                if (has_gamma) gamma4 = *(const float4*)(p.gamma + n);
-                if (has_res) {
-                    if constexpr (AHEAD) {
-                        if (q + 1 < NPASS) {
-                            const float* r1 = rptr(q + 1);
-#pragma unroll
-                            for (int k = 0; k < NKI; ++k) rnext[k] = ld_res4(r1 + (long)(k * RPI) * ldr);
-                        }
-                    } else {
-                        const float* r0 = rptr(q);
-#pragma unroll
-                        for (int k = 0; k < NKI; ++k) rcur[k] = ld_res4(r0 + (long)(k * RPI) * ldr);
-                    }
-                }
-                dump(i, g);
-                const long mrow = mbase + i * 32 + rsub;
-                const bool pad = p.out_op && p.map_op == ADA_MAP_PAD;
+            struct Pass {
+                int n;
+                ColConst<1> c;
+                long mrow;
+                bool pad;
                 PadWalk walk;
-                if (pad) walk = pad_start(p, (uint32_t)mrow);
-#pragma unroll
-                for (int k = 0; k < NKI; ++k) {
-                    float4 v = *(const float4*)(slab + (k * RPI + rsub) * SW + 4 * cg);
-                    v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w;
-                    if constexpr (EPI == EPI_GELU) {
-                        gelu_erf4(v);
-                    }
-                    v.x = v.x * gamma4.x + rcur[k].x; v.y = v.y * gamma4.y + rcur[k].y;
-                    v.z = v.z * gamma4.z + rcur[k].z; v.w = v.w * gamma4.w + rcur[k].w;
-                    if (p.out_f32) {
-                        float4 w = v;
-                        if (relu_f) {
-                            w.x = __builtin_fmaxf(w.x, 0.f); w.y = __builtin_fmaxf(w.y, 0.f);
-                            w.z = __builtin_fmaxf(w.z, 0.f); w.w = __builtin_fmaxf(w.w, 0.f);
-                        }
-                        st_f32x4(p.out_f32 + (mrow + k * RPI) * ldf + n, w);
-                    }
+            };
+            res_passes(
+                [=](int q, int k) -> const float* {
+                    const int g = q / TI, i = q - g * TI;
+                    return p.res + (long)(mbase + i * 32 + rsub) * ldr + (nwave + g * GW + 4 * cg) + (long)(k * RPI4) * ldr;
+                },
+                [=](int g, int i) {
+                    Pass st;
+                    st.n = nwave + g * GW + 4 * cg;
+                    st.c = col_const<1>(p, st.n);
+                    st.mrow = mbase + i * 32 + rsub;
+                    st.pad = p.out_op && p.map_op == ADA_MAP_PAD;
+                    return st;
+                },
+                [=](Pass& st, int k, float4 r) {
+                    // the walk's two divisions start behind the pass's dump(), under the latency of its LDS writes, not in front of it
+                    if (k == 0 && st.pad) st.walk = pad_start(p, (uint32_t)st.mrow);
+                    float4 v[1] = {*(const float4*)(slab + (k * RPI4 + rsub) * SW + 4 * cg)};
+                    epi_value<EPI, true>(v, st.c, &r);
+                    if (p.out_f32) *(float4*)(p.out_f32 + (st.mrow + k * RPI4) * ldf + st.n) = relu4_if(v[0], relu_f);
                     if (p.out_op) {
-                        if (relu_o) {
-                            v.x = __builtin_fmaxf(v.x, 0.f); v.y = __builtin_fmaxf(v.y, 0.f);
-                            v.z = __builtin_fmaxf(v.z, 0.f); v.w = __builtin_fmaxf(v.w, 0.f);
-                        }
-                        if (pad) {
-                            store_op4(p, p.out_op + walk.prow * ldo + n, n, v);
-                            pad_step(p, walk, RPI);
+                        const float4 o = relu4_if(v[0], relu_o);
+                        if (st.pad) {
+                            store_op4(p, p.out_op + st.walk.prow * ldo + st.n, st.n, o);
+                            pad_step(p, st.walk, RPI4);
                         } else {
-                            store_op4(p, p.out_op + (mrow + k * RPI) * ldo + n, n, v);
+                            store_op4(p, p.out_op + (st.mrow + k * RPI4) * ldo + st.n, st.n, o);
                         }
                     }
-                }
-                if constexpr (AHEAD) {
-                    if (has_res) {
-#pragma unroll
-                        for (int k = 0; k < NKI; ++k) rcur[k] = rnext[k];
-                    }
-                }
-            }
+                });
         }
     } else if (!p.out_f32 && !(flags & ADA_EP_RESIDUAL) && (p.ldo_op & 7) == 0 && (EPI != EPI_SHUFFLE || (p.shuffle_c & 7) == 0)) {
         // ---- operand-only output: 8 columns per lane -> one 16-byte store per row segment ----------------
@@ -853,21 +859,9 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4 && 
             const int n = nwave + g * GW + 8 * cg;
             const bool nval = n < p.N;
             const bool nval2 = n + 4 < p.N;
-            float4 b0 = make_float4(0, 0, 0, 0), b1 = b0, g0 = make_float4(1, 1, 1, 1), g1 = g0;
-            if (flags & ADA_EP_BIAS) {
-                if (nval) b0 = *(const float4*)(p.bias + n);
-                if (nval2) b1 = *(const float4*)(p.bias + n + 4);
-            }
-            if (flags & ADA_EP_GAMMA) {
-                if (nval) g0 = *(const float4*)(p.gamma + n);
-                if (nval2) g1 = *(const float4*)(p.gamma + n + 4);
-            }
-            uint32_t sh_i = 0, sh_j = 0, sh_co = 0;
-            if constexpr (EPI == EPI_SHUFFLE) {
-                uint32_t ij;
-                fast_divmod((uint32_t)(nval ? n : 0), p.dShC, ij, sh_co);
-                fast_divmod(ij, p.dShS, sh_i, sh_j);
-            }
+            ColConst<2> c = col_const<2>(p, n, nval, nval2);
+            ShufflePhase sh{};
+            if constexpr (EPI == EPI_SHUFFLE) sh = shuffle_phase(p, (uint32_t)(nval ? n : 0));
 #pragma unroll
             for (int i = 0; i < TI; ++i) {
                 dump(i, g);
@@ -875,160 +869,84 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4 && 
                 for (int k = 0; k < 32 / RPI; ++k) {
                     const int row = k * RPI + rsub;
                     const int m = mbase + i * 32 + row;
-                    float4 v0 = *(const float4*)(slab + row * SW + 8 * cg);
-                    float4 v1 = *(const float4*)(slab + row * SW + 8 * cg + 4);
+                    float4 v[2] = {*(const float4*)(slab + row * SW + 8 * cg), *(const float4*)(slab + row * SW + 8 * cg + 4)};
                     if (p.bias_row_mod > 0) {   // one bias vector per group of rows (the class-token read-out: a per-image bias, DA2/dpt.py:164-167)
                         uint32_t grp, rr_;
                         fast_divmod((uint32_t)(m < p.M ? m : p.M - 1), p.dBiasMod, grp, rr_);
                         const float* brow = p.bias + (long)grp * p.N;
-                        b0 = nval ? *(const float4*)(brow + n) : make_float4(0, 0, 0, 0);
-                        b1 = nval2 ? *(const float4*)(brow + n + 4) : make_float4(0, 0, 0, 0);
+                        c.b[0] = nval ? *(const float4*)(brow + n) : make_float4(0, 0, 0, 0);
+                        c.b[1] = nval2 ? *(const float4*)(brow + n + 4) : make_float4(0, 0, 0, 0);
                     }
-                    v0.x += b0.x; v0.y += b0.y; v0.z += b0.z; v0.w += b0.w;
-                    v1.x += b1.x; v1.y += b1.y; v1.z += b1.z; v1.w += b1.w;
-                    if constexpr (EPI == EPI_GELU) {
-                        gelu_erf4(v0);
-                        gelu_erf4(v1);
-                    }
-                    v0.x *= g0.x; v0.y *= g0.y; v0.z *= g0.z; v0.w *= g0.w;
-                    v1.x *= g1.x; v1.y *= g1.y; v1.z *= g1.z; v1.w *= g1.w;
+                    epi_value<EPI, false>(v, c, nullptr);
                     if (relu) {
-                        v0.x = __builtin_fmaxf(v0.x, 0.f); v0.y = __builtin_fmaxf(v0.y, 0.f); v0.z = __builtin_fmaxf(v0.z, 0.f); v0.w = __builtin_fmaxf(v0.w, 0.f);
-                        v1.x = __builtin_fmaxf(v1.x, 0.f); v1.y = __builtin_fmaxf(v1.y, 0.f); v1.z = __builtin_fmaxf(v1.z, 0.f); v1.w = __builtin_fmaxf(v1.w, 0.f);
+                        v[0] = relu4(v[0]);
+                        v[1] = relu4(v[1]);
                     }
                     if (m < p.M && nval) {
-                        long orow;
-                        int ocol = n;
-                        if constexpr (EPI == EPI_SHUFFLE) {
-                            uint32_t sb, rem, sy, sx;
-                            fast_divmod((uint32_t)m, p.dMapHW, sb, rem);
-                            fast_divmod(rem, p.dMapW, sy, sx);
-                            orow = ((long)sb * (p.shuffle_s * p.map_h + 2) + (p.shuffle_s * sy + sh_i + 1)) * (p.shuffle_s * p.map_w + 2) +
-                                   (p.shuffle_s * sx + sh_j + 1);
-                            ocol = (int)sh_co;
-                        } else {
-                            orow = map_row(p, p.map_op, (uint32_t)m);
-                        }
+                        const long orow = EPI == EPI_SHUFFLE ? shuffle_row(p, (uint32_t)m, sh) : map_row(p, p.map_op, (uint32_t)m);
+                        const int ocol = EPI == EPI_SHUFFLE ? (int)sh.co : n;
                         op_t* dst = p.out_op + orow * p.ldo_op + ocol;
-                        if (nval2) store_op8(p, dst, ocol, v0, v1);
-                        else store_op4<EPI != EPI_SHUFFLE>(p, dst, ocol, v0);   // (behind a shuffle the fp8 form needs shuffle_c % 8 == 0 -- validated -- so it never gets here:
+                        if (nval2) store_op8(p, dst, ocol, v[0], v[1]);
+                        else store_op4<EPI != EPI_SHUFFLE>(p, dst, ocol, v[0]);   // (behind a shuffle the fp8 form needs shuffle_c % 8 == 0 -- validated -- so it never gets here:
                                                                                  //  with its code in this branch too the 256x256 shuffle kernel spills two registers)
                     }
                 }
             }
         }
     } else {
-        // ---- fp32 output and/or residual: 4 columns per lane; the residual loads of a whole 32-row pass are issued
-        //      together (clamped, unconditional) one pass ahead, so their HBM latency hides behind the LDS transpose ----
-        constexpr int CG = GW / 4;       // float4 column groups per row (8 or 16)
-        constexpr int RPI = 64 / CG;     // rows covered by one wave-wide float4 read (8 or 4)
-        constexpr int NKI = 32 / RPI;
-        constexpr int NPASS = NG * TI;   // pass index q = g * TI + i
-        const int cg = lane % CG, rsub = lane / CG;
-        const bool has_res = (flags & ADA_EP_RESIDUAL) != 0;
-        auto col_of = [&](int g) { return nwave + g * GW + 4 * cg; };
-        auto res_ptr = [&](int q, int k) -> const float* {
-            const int g = q / TI, i = q - g * TI;
-            int m = mbase + i * 32 + k * RPI + rsub;
-            if (m >= p.M) m = p.M - 1;
-            int nc = col_of(g);
-            if (nc >= p.N) nc = 0;
-            long rrow;
-            if (p.res_row_mod > 0) {
-                uint32_t qq, rr;
-                fast_divmod((uint32_t)m, p.dResMod, qq, rr);
-                rrow = (long)rr + p.res_row_off;
-            } else {
-                rrow = map_row(p, p.map_f32, (uint32_t)m);
-            }
-            return p.res + rrow * p.ldr + nc;
+        // ---- fp32 output and/or residual: 4 columns per lane; residual addresses are clamped so that the loads are unconditional ----
+        const int cg = lane % CG4, rsub = lane / CG4;
+        struct Pass {
+            int mfirst, n;   // GEMM row of slab row 0, the lane's first column
+            bool nval;       // N % 4 == 0 is checked on the host
+            ColConst<1> c;
+            ShufflePhase sh;
         };
-        // one-pass-ahead prefetch only where a single workgroup owns the CU; with 2-3 co-resident workgroups the other
-        // workgroups' MFMAs already cover the latency and the 32 extra VGPRs would spill
-        constexpr bool AHEAD = (NWAVES == 8 && TJ <= 2) || PIPE4;
-        float4 rcur[NKI], rnext[AHEAD ? NKI : 1];
-#pragma unroll
-        for (int k = 0; k < NKI; ++k) rcur[k] = make_float4(0, 0, 0, 0);
-        if (AHEAD && has_res) {
-#pragma unroll
-            for (int k = 0; k < NKI; ++k) rcur[k] = *(const float4*)res_ptr(0, k);
-        }
-#pragma unroll
-        for (int q = 0; q < NPASS; ++q) {
-            const int g = q / TI, i = q - g * TI;
-            const int n = col_of(g);
-            const bool nval = n < p.N;       // N % 4 == 0 is checked on the host
-            const int nc = nval ? n : 0;
-            float4 bias4 = make_float4(0, 0, 0, 0), gamma4 = make_float4(1, 1, 1, 1);
-            if (flags & ADA_EP_BIAS) bias4 = *(const float4*)(p.bias + nc);
-            if (flags & ADA_EP_GAMMA) gamma4 = *(const float4*)(p.gamma + nc);
-            uint32_t sh_i = 0, sh_j = 0, sh_co = 0;
-            if constexpr (EPI == EPI_SHUFFLE) {
-                uint32_t ij;
-                fast_divmod((uint32_t)nc, p.dShC, ij, sh_co);
-                fast_divmod(ij, p.dShS, sh_i, sh_j);
-            }
-            if constexpr (AHEAD) {
-                if (has_res && q + 1 < NPASS) {
-#pragma unroll
-                    for (int k = 0; k < NKI; ++k) rnext[k] = *(const float4*)res_ptr(q + 1, k);
+        res_passes(
+            [=](int q, int k) -> const float* {
+                const int g = q / TI, i = q - g * TI;
+                int m = mbase + i * 32 + k * RPI4 + rsub;
+                if (m >= p.M) m = p.M - 1;
+                int nc = nwave + g * GW + 4 * cg;
+                if (nc >= p.N) nc = 0;
+                long rrow;
+                if (p.res_row_mod > 0) {
+                    uint32_t qq, rr;
+                    fast_divmod((uint32_t)m, p.dResMod, qq, rr);
+                    rrow = (long)rr + p.res_row_off;
+                } else {
+                    rrow = map_row(p, p.map_f32, (uint32_t)m);
                 }
-            } else {
-                if (has_res) {
-#pragma unroll
-                    for (int k = 0; k < NKI; ++k) rcur[k] = *(const float4*)res_ptr(q, k);
-                }
-            }
-            dump(i, g);
-#pragma unroll
-            for (int k = 0; k < NKI; ++k) {
-                const int row = k * RPI + rsub;
-                const int m = mbase + i * 32 + row;
-                float4 v = *(const float4*)(slab + row * SW + 4 * cg);
-                v.x += bias4.x; v.y += bias4.y; v.z += bias4.z; v.w += bias4.w;
-                if constexpr (EPI == EPI_GELU) {
-                    gelu_erf4(v);
-                }
-                v.x = v.x * gamma4.x + rcur[k].x; v.y = v.y * gamma4.y + rcur[k].y;
-                v.z = v.z * gamma4.z + rcur[k].z; v.w = v.w * gamma4.w + rcur[k].w;
-                if (m < p.M && nval) {
+                return p.res + rrow * p.ldr + nc;
+            },
+            [=](int g, int i) {
+                Pass st{};
+                st.mfirst = mbase + i * 32;
+                st.n = nwave + g * GW + 4 * cg;
+                st.nval = st.n < p.N;
+                const int nc = st.nval ? st.n : 0;
+                st.c = col_const<1>(p, nc);
+                if constexpr (EPI == EPI_SHUFFLE) st.sh = shuffle_phase(p, (uint32_t)nc);
+                return st;
+            },
+            [=](Pass& st, int k, float4 r) {
+                const int row = k * RPI4 + rsub;
+                const int m = st.mfirst + row;
+                float4 v[1] = {*(const float4*)(slab + row * SW + 4 * cg)};
+                epi_value<EPI, true>(v, st.c, &r);
+                if (m < p.M && st.nval) {
                     if (p.out_f32) {
                         const long frow = map_row(p, p.map_f32, (uint32_t)m);
-                        float4 w = v;
-                        if (flags & ADA_EP_RELU_F32) {
-                            w.x = __builtin_fmaxf(w.x, 0.f); w.y = __builtin_fmaxf(w.y, 0.f);
-                            w.z = __builtin_fmaxf(w.z, 0.f); w.w = __builtin_fmaxf(w.w, 0.f);
-                        }
-                        *(float4*)(p.out_f32 + frow * p.ldo_f32 + n) = w;
+                        *(float4*)(p.out_f32 + frow * p.ldo_f32 + st.n) = relu4_if(v[0], (flags & ADA_EP_RELU_F32) != 0);
                     }
                     if (p.out_op) {
-                        if (flags & ADA_EP_RELU_OP) {
-                            v.x = __builtin_fmaxf(v.x, 0.f); v.y = __builtin_fmaxf(v.y, 0.f);
-                            v.z = __builtin_fmaxf(v.z, 0.f); v.w = __builtin_fmaxf(v.w, 0.f);
-                        }
-                        long orow;
-                        int ocol = n;
-                        if constexpr (EPI == EPI_SHUFFLE) {
-                            uint32_t sb, rem, sy, sx;
-                            fast_divmod((uint32_t)m, p.dMapHW, sb, rem);
-                            fast_divmod(rem, p.dMapW, sy, sx);
-                            orow = ((long)sb * (p.shuffle_s * p.map_h + 2) + (p.shuffle_s * sy + sh_i + 1)) *
-                                       (p.shuffle_s * p.map_w + 2) + (p.shuffle_s * sx + sh_j + 1);
-                            ocol = (int)sh_co;
-                        } else {
-                            orow = map_row(p, p.map_op, (uint32_t)m);
-                        }
-                        store_op4<EPI != EPI_SHUFFLE>(p, p.out_op + orow * p.ldo_op + ocol, ocol, v);
+                        const float4 o = relu4_if(v[0], (flags & ADA_EP_RELU_OP) != 0);
+                        const long orow = EPI == EPI_SHUFFLE ? shuffle_row(p, (uint32_t)m, st.sh) : map_row(p, p.map_op, (uint32_t)m);
+                        const int ocol = EPI == EPI_SHUFFLE ? (int)st.sh.co : st.n;
+                        store_op4<EPI != EPI_SHUFFLE>(p, p.out_op + orow * p.ldo_op + ocol, ocol, o);
                     }
                 }
-            }
-            if constexpr (AHEAD) {
-                if (has_res) {
-#pragma unroll
-                    for (int k = 0; k < NKI; ++k) rcur[k] = rnext[k];
-                }
-            }
-        }
+            });
     }
     if (!PIPE4 && p.dbg && tid == 0) {
         const unsigned long long t_issued = __builtin_amdgcn_s_memtime();   // epilogue instructions issued, stores in flight
@@ -1324,7 +1242,6 @@ extern "C" int ada_igemm(const ada_igemm_args* a, void* stream) {
     d.dShC = make_fastdiv(a->shuffle_c > 0 ? a->shuffle_c : 1);
     d.dShS = make_fastdiv(a->shuffle_s > 0 ? a->shuffle_s : 1);
     d.tail_w = a->tail_w; d.tail_b = a->tail_b; d.tail_act = a->tail_act;
-    d.cps = 0;
     d.group_n = 1;
     d.tiles_m = d.tiles_n = 0;
 

@@ -368,6 +368,7 @@ def saturation_family(M=300, N=128, K=64):
 
 
 CONV_RES_CASES = [(2, 64, 21, 17, 64, 1), (2, 128, 37, 37, 128, 2)]
+CONV_RES_WIDE_CASE = (1, 64, 17, 16, 256, 1)   # M = 272, N = 256: on the 256- and 128-row tiles interior tiles and one edge tile
 
 
 @functools.lru_cache(maxsize=None)

@@ -95,7 +95,7 @@ def _families():
     out = [("a_dup_seg", X.a_dup_family, ()), ("a_wrap", X.a_wrap_family, ()), ("saturation", X.saturation_family, ()),
            ("token map", X.token_map_family, X.TOKEN_MAP_CASE), ("split pad", X.split_pad_family, ()), ("split shuffle", X.shuffle_family, X.SPLIT_SHUFFLE_CASE),
            ("tail", X.tail_family, (False,)), ("sigmoid tail", X.tail_family, (True,))]
-    out += [("conv + residual", X.conv_res_family, c) for c in X.CONV_RES_CASES]
+    out += [("conv + residual", X.conv_res_family, c) for c in X.CONV_RES_CASES + [X.CONV_RES_WIDE_CASE]]
     out += [("conv transpose", X.shuffle_family, c) for c in X.SHUFFLE_CASES]
     out += [("sub-pixel", X.subpixel_family, c[:5]) for c in X.SUBPIXEL_CASES[:2]]
     out += [("bilinear", X.bilinear_family, c) for c in X.BILINEAR_CASES]

@@ -315,30 +315,38 @@ def test_igemm_exact_f8_from(hip, forced_tile, cfg, variant):
 
 
 # ---- geometry -------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("B,C,H,W_,Co,stride", X.CONV_RES_CASES)
-def test_igemm_exact_conv3x3_padded_output_and_residual(hip, B, C, H, W_, Co, stride):
+SMALL_TILES = [(0, 4), (1, 4), (-1, 0)]            # the narrow tiles + the heuristic's own choice, for shapes too small for the wide tiles
+WIDE_TILES = [(2, 4), (3, 4), (3, 16), (4, 4)]
+CONV_RES_RUNS = [(c, t) for c in X.CONV_RES_CASES for t in SMALL_TILES] + [(X.CONV_RES_WIDE_CASE, t) for t in WIDE_TILES]
+
+
+@pytest.mark.parametrize("case,tile", CONV_RES_RUNS)
+def test_igemm_exact_conv3x3_padded_output_and_residual(hip, forced_tile, case, tile):
+    """The padded-grid row map and the residual addresses on every tile shape: interior and edge tiles of each (the wide case: M = 272 rows)."""
+    (B, C, H, W_, Co, stride), (cfg, variant) = case, tile
     op = _op(hip)
     c = X.conv_res_family(B, C, H, W_, Co, stride)
     Ho, Wo, v = c["Ho"], c["Wo"], c["ref"]
     assert_exact_budget(mag=c["mag"], unit=c["unit"], ref=v, what="conv3x3")
     of = torch.full((B * Ho * Wo, Co), GUARD, device=DEV)
     op_ = torch.zeros(B, Ho + 2, Wo + 2, Co, dtype=op, device=DEV)
-    hip.igemm(M=B * Ho * Wo, N=Co, K=9 * C, A=_pad_nhwc(c["x"], C, op).to(DEV), lda=C, W=_pack3(c["w"], C, op).to(DEV), a_mode=hip.A_CONV3,
-              conv=(Ho, Wo, H + 2, W_ + 2, stride), bias=c["bias"].to(DEV), res=c["res"].to(DEV), ldr=Co, flags=hip.EP_BIAS | hip.EP_RESIDUAL | hip.EP_RELU_OP,
-              out_f32=of, ldo_f32=Co, out_op=op_, ldo_op=Co, map_op=hip.MAP_PAD, map_h=Ho, map_w=Wo)
+    _run(hip, forced_tile, cfg, variant, M=B * Ho * Wo, N=Co, K=9 * C, A=_pad_nhwc(c["x"], C, op).to(DEV), lda=C, W=_pack3(c["w"], C, op).to(DEV), a_mode=hip.A_CONV3,
+         conv=(Ho, Wo, H + 2, W_ + 2, stride), bias=c["bias"].to(DEV), res=c["res"].to(DEV), ldr=Co, flags=hip.EP_BIAS | hip.EP_RESIDUAL | hip.EP_RELU_OP,
+         out_f32=of, ldo_f32=Co, out_op=op_, ldo_op=Co, map_op=hip.MAP_PAD, map_h=Ho, map_w=Wo)
     assert_bits(of, v, f"conv3x3 stride {stride} f32")
     assert_bits(op_[:, 1:-1, 1:-1].reshape(-1, Co), rne(v.clamp_min(0), op), f"conv3x3 stride {stride} relu padded")
     _border_zero(op_, "conv3x3")
 
 
-def test_igemm_exact_token_map_with_pos(hip):
+@pytest.mark.parametrize("cfg,variant", SMALL_TILES)
+def test_igemm_exact_token_map_with_pos(hip, forced_tile, cfg, variant):
     op = _op(hip)
     B, Np, D, K = X.TOKEN_MAP_CASE
     f = X.token_map_family(B, Np, D, K)
     assert_exact_budget(mag=f["mag"], unit=f["unit"], ref=f["ref"], what="token map")
     x = torch.full((B * (Np + 1), D), GUARD, device=DEV)
-    hip.igemm(M=B * Np, N=D, K=K, A=f["A"].to(op).to(DEV), lda=K, W=f["W"].to(op).to(DEV), bias=f["bias"].to(DEV), res=f["pos"].to(DEV), ldr=D, res_row_mod=Np, res_row_off=1,
-              flags=hip.EP_BIAS | hip.EP_RESIDUAL, out_f32=x, ldo_f32=D, map_f32=hip.MAP_TOKEN, map_h=Np)
+    _run(hip, forced_tile, cfg, variant, M=B * Np, N=D, K=K, A=f["A"].to(op).to(DEV), lda=K, W=f["W"].to(op).to(DEV), bias=f["bias"].to(DEV), res=f["pos"].to(DEV), ldr=D,
+         res_row_mod=Np, res_row_off=1, flags=hip.EP_BIAS | hip.EP_RESIDUAL, out_f32=x, ldo_f32=D, map_f32=hip.MAP_TOKEN, map_h=Np)
     got = x.reshape(B, Np + 1, D).cpu()
     assert_bits(got[:, 1:], f["ref"], "token map")
     assert bool((got[:, 0] == GUARD).all()), "cls rows written"
