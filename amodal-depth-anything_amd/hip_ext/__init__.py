@@ -32,6 +32,7 @@ EXPORTS = (
     "ada_image_prep_fwd", "ada_depth_resize_fwd",
     "ada_photo_prep_fwd", "ada_mask_prep_fwd", "ada_nearest_resize_fwd", "ada_blend_ex", "ada_depth_render_fwd",
     "ada_pil_resize_u8_fwd", "ada_label_combine_fwd",
+    "ada_mask_label_fwd", "ada_mask_stats_fwd", "ada_mask_keep_area_fwd", "ada_mask_grid_points_fwd",
     "ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_last_tile",
     "ada_debug_set_timestamps", "ada_debug_set_attention_variant", "ada_debug_count_saturated",
 )
@@ -184,6 +185,14 @@ def load(path: Optional[str] = None):
     lib.ada_label_combine_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                           c_void_p, c_void_p]
     lib.ada_label_combine_fwd.restype = c_int
+    lib.ada_mask_label_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.ada_mask_label_fwd.restype = c_int
+    lib.ada_mask_stats_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.ada_mask_stats_fwd.restype = c_int
+    lib.ada_mask_keep_area_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.ada_mask_keep_area_fwd.restype = c_int
+    lib.ada_mask_grid_points_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]
+    lib.ada_mask_grid_points_fwd.restype = c_int
     for name in ("ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_set_attention_variant"):
         getattr(lib, name).argtypes = [c_int]
         getattr(lib, name).restype = None
@@ -680,6 +689,82 @@ def label_combine(whole, occ, whole_mask, scale_shift, out_u16, out_f32=None, ou
                                         _dev(scale_shift, "scale_shift", torch.float32), P, h, w, ho, wo, int(overflow), _dev(out_u16, "out_u16", torch.uint16),
                                         _opt(out_f32, "out_f32", torch.float32), _opt(out_of_range, "out_of_range", torch.int32), _stream()),
            "ada_label_combine_fwd")
+
+
+def mask_label_workspace_bytes(batch: int, h: int, w: int) -> int:
+    """Bytes of workspace ada_mask_label_fwd asks for (include/ada_hip.h)."""
+    return 4 * batch * (2 * h * w + (h * w + 1023) // 1024)
+
+
+def mask_keep_area_workspace_bytes(batch: int, h: int, w: int) -> int:
+    """Bytes of workspace ada_mask_keep_area_fwd asks for: the areas of labels 0 .. ceil(h * w / 2) per image."""
+    return 4 * batch * (h * w // 2 + 2)
+
+
+def _label_map(who, labels):
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or not labels.is_contiguous():
+        raise HipExtError(f"{who}: labels must be a contiguous int32 [K, h, w] tensor, got {tuple(getattr(labels, 'shape', ()))}")
+    _dev(labels, "labels", torch.int32)
+    return tuple(labels.shape)
+
+
+def _sized(who, name, t, shape, dtype):
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise HipExtError(f"{who}: {name} must be a contiguous {tuple(shape)} tensor, got {tuple(getattr(t, 'shape', ()))}")
+    return _dev(t, name, dtype)
+
+
+def _bytes_of(who, workspace, need, device):
+    if workspace is None:
+        workspace = torch.empty((need + 3) // 4, dtype=torch.int32, device=device)
+    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != device:
+        raise HipExtError(f"{who}: workspace must be a contiguous tensor on {device}")
+    return workspace, workspace.numel() * workspace.element_size()
+
+
+def mask_label(src, batch, h, w, row_pitch, image_stride, connectivity, labels, n_labels, workspace=None):
+    """uint8 masks [batch][h][w] (rows ``row_pitch`` bytes, images ``image_stride`` bytes apart; non-zero = inside) -> labels int32 [batch, h, w] (0 =
+    background, components 1 .. n in the raster order of their first pixels) and n_labels int32 [batch] (ada_mask_label_fwd).  ``workspace``: any
+    contiguous device tensor of at least mask_label_workspace_bytes(batch, h, w) bytes, allocated when None."""
+    who = "mask_label"
+    _check_src_extent(who, src, (batch - 1) * image_stride + (h - 1) * row_pitch + w)
+    pl, pn = _sized(who, "labels", labels, (batch, h, w), torch.int32), _sized(who, "n_labels", n_labels, (batch,), torch.int32)
+    ws, ws_bytes = _bytes_of(who, workspace, mask_label_workspace_bytes(batch, h, w), labels.device)
+    _check(load().ada_mask_label_fwd(_dev(src, "src", torch.uint8), batch, h, w, row_pitch, image_stride, int(connectivity), pl, pn, ws.data_ptr(), ws_bytes,
+                                     _stream()), "ada_mask_label_fwd")
+
+
+def mask_stats(labels, max_labels, stats, sums):
+    """labels int32 [K, h, w] -> stats int32 [K, max_labels + 1, 5] (LEFT, TOP, WIDTH, HEIGHT, AREA) and sums int64 [K, max_labels + 1, 2] = (sum x, sum y);
+    row 0 is the background, rows without pixels are zero, labels above max_labels are ignored (ada_mask_stats_fwd)."""
+    K, h, w = _label_map("mask_stats", labels)
+    ps = _sized("mask_stats", "stats", stats, (K, max_labels + 1, 5), torch.int32)
+    pm = _sized("mask_stats", "sums", sums, (K, max_labels + 1, 2), torch.int64)
+    _check(load().ada_mask_stats_fwd(labels.data_ptr(), K, h, w, int(max_labels), ps, pm, _stream()), "ada_mask_stats_fwd")
+
+
+def mask_keep_area(labels, min_area, out_u8=None, out_f32=None, workspace=None):
+    """labels int32 [K, h, w] -> out_u8 uint8 / out_f32 fp32 0 / 1 [K, h, w] = label != 0 and area(label) >= min_area (ada_mask_keep_area_fwd)."""
+    who = "mask_keep_area"
+    K, h, w = _label_map(who, labels)
+    if out_u8 is None and out_f32 is None:
+        raise HipExtError(f"{who}: out_u8 and out_f32 are both None")
+    pu = None if out_u8 is None else _sized(who, "out_u8", out_u8, (K, h, w), torch.uint8)
+    pf = None if out_f32 is None else _sized(who, "out_f32", out_f32, (K, h, w), torch.float32)
+    ws, ws_bytes = _bytes_of(who, workspace, mask_keep_area_workspace_bytes(K, h, w), labels.device)
+    _check(load().ada_mask_keep_area_fwd(labels.data_ptr(), K, h, w, int(min_area), pu, pf, ws.data_ptr(), ws_bytes, _stream()), "ada_mask_keep_area_fwd")
+
+
+def mask_grid_points(labels, stats, small_component_thresh, grid_step, hit):
+    """labels int32 [K, h, w], stats int32 [K, cap + 1, 5] -> hit int32 [K, h, w]: the label at the grid points of the components of at least
+    ``small_component_thresh`` pixels, 0 elsewhere (ada_mask_grid_points_fwd)."""
+    who = "mask_grid_points"
+    K, h, w = _label_map(who, labels)
+    if not isinstance(stats, torch.Tensor) or stats.dim() != 3 or stats.shape[0] != K or stats.shape[1] < 1 or stats.shape[2] != 5 or not stats.is_contiguous():
+        raise HipExtError(f"{who}: stats must be a contiguous int32 [{K}, cap + 1, 5] tensor, got {tuple(getattr(stats, 'shape', ()))}")
+    ph = _sized(who, "hit", hit, (K, h, w), torch.int32)
+    _check(load().ada_mask_grid_points_fwd(labels.data_ptr(), _dev(stats, "stats", torch.int32), K, h, w, stats.shape[1] - 1, int(small_component_thresh),
+                                           int(grid_step), ph, _stream()), "ada_mask_grid_points_fwd")
 
 
 # --- tuning / diagnostic hooks (include/ada_hip.h, last section) ---------------------------------

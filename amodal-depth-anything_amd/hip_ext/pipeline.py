@@ -76,7 +76,7 @@ def fit_scale_shift(amodal: torch.Tensor, base: torch.Tensor, visible: torch.Ten
 
 @torch.no_grad()
 def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None, size: int = 518, out_size=None, check: bool = True,
-                       render: bool = False):
+                       render: bool = False, min_area=None, min_area_connectivity: int = 4):
     """The reference's infer.py call on the device: a decoded uint8 BGR(A) photo [h, w, 3 | 4] and K amodal masks (uint8 / bool [h, w] or
     [K, h, w]) in, an AmodalResult out.  The base network runs once (B = 1), the amodal network once as a batch of K.
 
@@ -87,7 +87,10 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
     out_size: None (size x size), (h, w) or "image" (the photo's size): base and blended go through cv2's INTER_NEAREST rule (infer.py:77, 113).
     An all-zero amodal mask is legal: its blended map equals base.
     render=True: an AmodalRendered -- the same five fields plus the two pictures of infer.py:106-119 (hip_ext.image.render_depth: Spectral_r, the
-    outline and overlay of highlight_target on the amodal ones, B, G, R), rendered from the network-size maps straight to out_size."""
+    outline and overlay of highlight_target on the amodal ones, B, G, R), rendered from the network-size maps straight to out_size.
+    min_area: when given, the AMODAL masks are first cleaned as given, at their own resolution, by hip_ext.masks.remove_small_noise (the demo's
+    filter, app.py:283-293: components of fewer than min_area pixels under min_area_connectivity go) -- specks of a segmenter's mask would otherwise be
+    guidance for the network and receive pasted depth.  The visible masks are not touched.  None: nothing runs, the call is exactly the one without it."""
     from .image import _as_int, _check_size, masks_to_tensor, photo_to_inputs, render_depth, resize_nearest
     size = _check_size(size, "amodal_infer_image")
     if not (out_size is None or (isinstance(out_size, str) and out_size == "image")
@@ -95,6 +98,9 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
         raise ValueError(f"amodal_infer_image: out_size must be None, 'image' or (h, w), got {out_size!r}")
     device = next(amodal_model.parameters()).device
     rgb_raw, rgb, (h, w) = photo_to_inputs(image, size, device)
+    if min_area is not None:
+        from .masks import remove_small_noise
+        masks = remove_small_noise(masks, min_area=min_area, connectivity=min_area_connectivity, device=device)
     mask01, guide = masks_to_tensor(masks, size, device, guide=True)
     K, S = mask01.shape[0], size
     visible = None

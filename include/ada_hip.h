@@ -582,6 +582,47 @@ int ada_label_combine_fwd(const float* whole, const float* occ, const uint8_t* w
                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The demo's mask front-end (reference app.py): connected components of a mask on the device, their statistics, the area filter of remove_small_noise
+ * (app.py:283-293) and the prompt-point grid of get_points_from_components (app.py:77-99), which the reference does on the host with
+ * cv2.connectedComponents / connectedComponentsWithStats.  Additions under ABI 10.  Integer arithmetic only: every result is exact and bit-reproducible.
+ * The launch sequence of each call depends on the shapes alone (no host read, no flag loop, no cooperative launch): all four are legal inside a stream
+ * capture.  The library allocates nothing.  h * w < 2^31, batch <= 65535, h and w down to 1.
+ *   ada_mask_label_fwd       mask uint8 [batch][h][w], rows row_pitch_bytes apart (>= w), images image_stride_bytes apart, as ada_mask_prep_fwd: a crop is
+ *     read in place; any non-zero byte is inside.  connectivity: 4 or 8 (anything else: ADA_EINVAL).
+ *     labels     int32 [batch][h][w] packed: 0 = background, components numbered 1 .. n IN THE RASTER ORDER OF EACH COMPONENT'S FIRST PIXEL (row-major).
+ *                That is scipy.ndimage.label's numbering.  OpenCV's documentation does not specify the numbering of connectedComponents, so nothing
+ *                here claims label-for-label equality with cv2 -- only the same partition; what the reference derives from the labels (the kept
+ *                pixels, the list of points up to the order of the components) depends on the partition alone.
+ *     n_labels   int32 [batch] on the device: n per image
+ *     workspace  the caller's, workspace_bytes >= 4 * batch * (2 * h * w + ceil(h * w / 1024)) (checked)
+ *     Algorithm: a union-find over pixel indices whose links always point to a smaller-or-equal index (union by integer atomic min), so every pointer
+ *     chase strictly decreases, every failed retry means some link decreased, no workgroup ever waits for another, and a component's root is its first
+ *     raster pixel: the numbering is a prefix count over root flags.  32 x 32 tiles in LDS, one pass over the tile borders, resolve, count, number,
+ *     paint: six launches (csrc/ada_masks.hip).
+ *   ada_mask_stats_fwd       from a label map and a capacity max_labels >= 0:
+ *     stats      int32 [batch][max_labels + 1][5] in cv2's column order (CC_STAT_LEFT, TOP, WIDTH, HEIGHT, AREA)
+ *     sums       int64 [batch][max_labels + 1][2] = (sum of x, sum of y) over the component's pixels; centroid = sums / area, cv2's (x, y) order
+ *     Row 0 is the background, as in connectedComponentsWithStats.  A row without pixels -- an empty background included -- is all zeros (this
+ *     library's definition; cv2's row for an empty background is not pinned).  Pixels whose label exceeds max_labels (or is negative) are ignored: the
+ *     caller detects the overflow from n_labels.  Runs of equal labels along a row are summed in registers and flushed with one set of integer atomics.
+ *   ada_mask_keep_area_fwd   from a label map: keep = label != 0 && area(label) >= min_area (remove_small_noise's rule), exact for any number of components.
+ *     out_u8     uint8 0 / 1 [batch][h][w], out_f32 fp32 0 / 1 [batch][h][w]: either may be NULL, not both
+ *     workspace  the per-label areas, workspace_bytes >= 4 * batch * (h * w / 2 + 2) (checked): a grid of h x w pixels holds at most ceil(h * w / 2)
+ *                components under either connectivity.  No capacity argument, no host read.
+ *   ada_mask_grid_points_fwd from a label map and ada_mask_stats_fwd's stats (same max_labels):
+ *     hit        int32 [batch][h][w] = label where area(label) >= small_component_thresh && (y - top) % grid_step == 0 && y < top + height - 1
+ *                && (x - left) % grid_step == 0 && x < left + width - 1, else 0.  This is range(min_y, max_y, grid_step) x range(min_x, max_x, grid_step) of
+ *                app.py:94-97, which EXCLUDES the last row and column of the bounding box: a large component one pixel wide yields no point.  grid_step >= 1.
+ * ---------------------------------------------------------------------------------------- */
+int ada_mask_label_fwd(const uint8_t* mask, int32_t batch, int32_t h, int32_t w, int64_t row_pitch_bytes, int64_t image_stride_bytes,
+                       int32_t connectivity, int32_t* labels, int32_t* n_labels, void* workspace, int64_t workspace_bytes, void* stream);
+int ada_mask_stats_fwd(const int32_t* labels, int32_t batch, int32_t h, int32_t w, int32_t max_labels, int32_t* stats, int64_t* sums, void* stream);
+int ada_mask_keep_area_fwd(const int32_t* labels, int32_t batch, int32_t h, int32_t w, int32_t min_area, uint8_t* out_u8, float* out_f32,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+int ada_mask_grid_points_fwd(const int32_t* labels, const int32_t* stats, int32_t batch, int32_t h, int32_t w, int32_t max_labels,
+                             int32_t small_component_thresh, int32_t grid_step, int32_t* hit, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Tiled inference for inputs larger than the network's native 518 x 518 (the reference squashes every
  * input to 518 x 518, infer.py:17,84).  ada_tile_blend_fwd merges the per-tile predictions:
  *   tiles     fp32 [B, T, tile_h, tile_w]; tile t covers rows origin_y[t].. and columns origin_x[t].. of the full map
