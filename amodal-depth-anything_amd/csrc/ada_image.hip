@@ -480,3 +480,98 @@ extern "C" int ada_depth_render_fwd(const float* depth, int32_t batch, int32_t h
         hipLaunchKernelGGL(depth_render_kernel<1>, dim3((unsigned)((wo + 63) / 64), (unsigned)((ho + 3) / 4), (unsigned)batch), block, 0, (hipStream_t)stream, a);
     return ada_check_launch("ada_depth_render_fwd");
 }
+
+// ---- the maps behind the quantiles (ada_quantile.hip): the normalizer's scale-and-shift and the reference's colorize() ----
+namespace {
+
+struct RangeMapArgs {
+    const float* d;
+    const float* range;      // [batch, 2]
+    float* out;
+    long n;
+    float scale, shift, clip_lo, clip_hi;
+    int clip;
+};
+
+// ScaleShiftDepthNormalizer.__call__ (src/util/depth_transform.py:87-94): four torch ops, each rounded to fp32, then torch.clip (NaN passes)
+__global__ __launch_bounds__(256) void range_map_kernel(RangeMapArgs a) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y;
+    const float lo = a.range[2 * b], span = a.range[2 * b + 1] - lo;
+    const float* d = a.d + (long)b * a.n;
+    float* o = a.out + (long)b * a.n;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
+        float t = (d[i] - lo) / span;
+        t = t * a.scale;
+        t = t + a.shift;
+        if (a.clip) t = t < a.clip_lo ? a.clip_lo : (t > a.clip_hi ? a.clip_hi : t);
+        o[i] = t;
+    }
+}
+
+struct ColorizeArgs {
+    const float* value;
+    const double* range;     // [batch, 2] or NULL
+    const uint8_t* lut;      // [256][4]
+    const uint8_t* invalid;  // [batch, h * w] or NULL
+    uint32_t* out;           // [batch, h * w] RGBA pixels
+    long n;
+    double vmin, vmax, invalid_val;
+    uint32_t background;
+};
+
+// colorize() (src/scripts/colorize_depth.py:50-75) on the map promoted to double; the table sits in LDS as pixels
+__global__ __launch_bounds__(256) void depth_colorize_kernel(ColorizeArgs a) {
+#pragma clang fp contract(off)
+    __shared__ uint32_t lut[256];
+    lut[threadIdx.x] = reinterpret_cast<const uint32_t*>(a.lut)[threadIdx.x];
+    __syncthreads();
+    const int b = blockIdx.y;
+    const double vmin = a.range ? a.range[2 * b] : a.vmin, vmax = a.range ? a.range[2 * b + 1] : a.vmax;
+    const bool flat = !(vmin != vmax);       // `if vmin != vmax`: a NaN bound normalises (and every t is NaN)
+    const double span = vmax - vmin;
+    const long base = (long)b * a.n;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
+        const double v = (double)a.value[base + i];
+        const bool bad = a.invalid ? a.invalid[base + i] != 0 : v == a.invalid_val;
+        uint32_t px = a.background;
+        if (!bad) {
+            const double t = flat ? v * 0.0 : (v - vmin) / span;
+            if (t != t) px = 0u;
+            else if (t < 0.0) px = lut[0];
+            else if (t >= 1.0) px = lut[255];
+            else px = lut[(int)(t * 256.0)];     // t in [0, 1): the index is 0 .. 255
+        }
+        a.out[base + i] = px;
+    }
+}
+
+}  // namespace
+
+extern "C" int ada_range_map_fwd(const float* d, const float* range, int32_t batch, int64_t n_per_image, float scale, float shift, int32_t clip,
+                                 float clip_lo, float clip_hi, float* out, void* stream) {
+    ADA_REQUIRE(d && range && out, ADA_EINVAL, "ada_range_map_fwd: null pointer");
+    ADA_REQUIRE(batch > 0 && n_per_image > 0, ADA_EINVAL, "ada_range_map_fwd: bad shape batch=%d n=%ld", batch, (long)n_per_image);
+    ADA_REQUIRE(batch <= 65535, ADA_EUNSUPPORTED, "ada_range_map_fwd: batch exceeds the grid limit");
+    RangeMapArgs a;
+    a.d = d; a.range = range; a.out = out; a.n = (long)n_per_image;
+    a.scale = scale; a.shift = shift; a.clip = clip ? 1 : 0; a.clip_lo = clip_lo; a.clip_hi = clip_hi;
+    const int64_t blocks = (n_per_image + 255) / 256;
+    hipLaunchKernelGGL(range_map_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096), (unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
+    return ada_check_launch("ada_range_map_fwd");
+}
+
+extern "C" int ada_depth_colorize_fwd(const float* value, int32_t batch, int32_t h, int32_t w, const double* range, double vmin, double vmax,
+                                      const uint8_t* lut, const uint8_t* invalid_mask, double invalid_val, uint32_t background_rgba, uint8_t* out,
+                                      void* stream) {
+    ADA_REQUIRE(value && lut && out, ADA_EINVAL, "ada_depth_colorize_fwd: null pointer");
+    ADA_REQUIRE(batch > 0 && h > 0 && w > 0, ADA_EINVAL, "ada_depth_colorize_fwd: bad shape batch=%d %dx%d", batch, h, w);
+    ADA_REQUIRE(batch <= 65535, ADA_EUNSUPPORTED, "ada_depth_colorize_fwd: batch exceeds the grid limit");
+    ADA_REQUIRE((uintptr_t)lut % 4 == 0 && (uintptr_t)out % 4 == 0, ADA_EINVAL, "ada_depth_colorize_fwd: lut and out must be 4-byte aligned");
+    ColorizeArgs a;
+    a.value = value; a.range = range; a.lut = lut; a.invalid = invalid_mask; a.out = reinterpret_cast<uint32_t*>(out);
+    a.n = (long)h * w; a.vmin = vmin; a.vmax = vmax; a.invalid_val = invalid_val; a.background = background_rgba;
+    const long blocks = (a.n + 255) / 256;
+    hipLaunchKernelGGL(depth_colorize_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096), (unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
+    return ada_check_launch("ada_depth_colorize_fwd");
+}

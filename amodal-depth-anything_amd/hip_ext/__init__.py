@@ -33,6 +33,7 @@ EXPORTS = (
     "ada_photo_prep_fwd", "ada_mask_prep_fwd", "ada_nearest_resize_fwd", "ada_blend_ex", "ada_depth_render_fwd",
     "ada_pil_resize_u8_fwd", "ada_label_combine_fwd",
     "ada_mask_label_fwd", "ada_mask_stats_fwd", "ada_mask_keep_area_fwd", "ada_mask_grid_points_fwd",
+    "ada_quantile_fwd", "ada_range_map_fwd", "ada_depth_colorize_fwd",
     "ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_last_tile",
     "ada_debug_set_timestamps", "ada_debug_set_attention_variant", "ada_debug_count_saturated",
 )
@@ -49,6 +50,12 @@ PROTOCOL_WS_DOUBLES = 32
 # ada_pil_resize_u8_fwd's filters (Pillow's own numbers) and ada_label_combine_fwd's casts
 PIL_NEAREST, PIL_BICUBIC = 0, 3
 LABEL_WRAP, LABEL_CLIP = 0, 1
+# ada_quantile_fwd: modes, population flags, quantiles per call, elements per workgroup, bytes of workspace per image
+Q_NUMPY, Q_TORCH = 0, 1
+Q_EXCLUDE_VALUE, Q_POSITIVE_ONLY = 0x1, 0x2
+QUANTILE_MAX_Q = 4
+QUANTILE_CHUNK = 4096
+QUANTILE_WS_BYTES_PER_IMAGE = 33792
 
 
 class IgemmArgs(ctypes.Structure):
@@ -193,6 +200,14 @@ def load(path: Optional[str] = None):
     lib.ada_mask_keep_area_fwd.restype = c_int
     lib.ada_mask_grid_points_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]
     lib.ada_mask_grid_points_fwd.restype = c_int
+    lib.ada_quantile_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int64, ctypes.POINTER(c_double), c_int32, c_int32, c_int32, c_double, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_int64, c_void_p]
+    lib.ada_quantile_fwd.restype = c_int
+    lib.ada_range_map_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int64, c_float, c_float, c_int32, c_float, c_float, c_void_p, c_void_p]
+    lib.ada_range_map_fwd.restype = c_int
+    lib.ada_depth_colorize_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_double, c_double, c_void_p, c_void_p, c_double, ctypes.c_uint32,
+                                           c_void_p, c_void_p]
+    lib.ada_depth_colorize_fwd.restype = c_int
     for name in ("ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_set_attention_variant"):
         getattr(lib, name).argtypes = [c_int]
         getattr(lib, name).restype = None
@@ -765,6 +780,78 @@ def mask_grid_points(labels, stats, small_component_thresh, grid_step, hit):
     ph = _sized(who, "hit", hit, (K, h, w), torch.int32)
     _check(load().ada_mask_grid_points_fwd(labels.data_ptr(), _dev(stats, "stats", torch.int32), K, h, w, stats.shape[1] - 1, int(small_component_thresh),
                                            int(grid_step), ph, _stream()), "ada_mask_grid_points_fwd")
+
+
+def quantile_workspace_bytes(batch: int) -> int:
+    """Bytes of workspace ada_quantile_fwd asks for (include/ada_hip.h)."""
+    return batch * QUANTILE_WS_BYTES_PER_IMAGE
+
+
+def quantile_select(x, q, out, out_f32=None, count=None, valid=None, mode=Q_NUMPY, flags=0, exclude_value=0.0, workspace=None):
+    """x fp32 [B, ...] contiguous -> out fp64 [B, len(q)], optionally out_f32 fp32 [B, len(q)] and count int64 [B]: the exact quantiles ``q`` (fractions
+    in [0, 1], at most QUANTILE_MAX_Q) of each image's population (ada_quantile_fwd).  ``valid``: uint8 of x's shape or None; ``workspace``: any
+    contiguous device tensor of at least quantile_workspace_bytes(B) bytes, allocated when None.  Nothing is read back."""
+    who = "quantile_select"
+    if not isinstance(x, torch.Tensor) or x.dim() < 1 or not x.is_contiguous() or x.numel() == 0:
+        raise HipExtError(f"{who}: x must be a non-empty contiguous fp32 [B, ...] tensor, got {tuple(getattr(x, 'shape', ()))}")
+    px = _dev(x, "x", torch.float32)
+    B = x.shape[0]
+    n = x.numel() // B
+    qs = [float(v) for v in q]
+    if not 1 <= len(qs) <= QUANTILE_MAX_Q:
+        raise HipExtError(f"{who}: {len(qs)} quantiles, 1..{QUANTILE_MAX_Q} per call")
+    nq = len(qs)
+    po = _sized(who, "out", out, (B, nq), torch.float64)
+    pf = None if out_f32 is None else _sized(who, "out_f32", out_f32, (B, nq), torch.float32)
+    pc = None if count is None else _sized(who, "count", count, (B,), torch.int64)
+    pv = None
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.shape != x.shape or not valid.is_contiguous() or valid.device != x.device:
+            raise HipExtError(f"{who}: valid must be a contiguous uint8 {tuple(x.shape)} tensor on {x.device}, got {tuple(getattr(valid, 'shape', ()))}")
+        pv = _dev(valid, "valid", torch.uint8)
+    for name, t in (("out", out), ("out_f32", out_f32), ("count", count)):
+        if t is not None and t.device != x.device:
+            raise HipExtError(f"{who}: {name} on {t.device}, x on {x.device}")
+    ws, ws_bytes = _bytes_of(who, workspace, quantile_workspace_bytes(B), x.device)
+    _check(load().ada_quantile_fwd(px, pv, B, n, (c_double * nq)(*qs), nq, int(mode), int(flags), float(exclude_value), po, pf, pc, ws.data_ptr(), ws_bytes,
+                                   _stream()), "ada_quantile_fwd")
+
+
+def range_map(depth, range32, out, scale=1.0, shift=0.0, clip=None):
+    """out = ((depth - lo) / (hi - lo)) * scale + shift per image, clamped to ``clip`` = (lo, hi) when given; (lo, hi) of the map from ``range32``, device
+    fp32 [B, 2] (ada_range_map_fwd).  depth, out: contiguous fp32 [B, ...] of one shape."""
+    who = "range_map"
+    if not isinstance(depth, torch.Tensor) or depth.dim() < 1 or not depth.is_contiguous() or depth.numel() == 0:
+        raise HipExtError(f"{who}: depth must be a non-empty contiguous fp32 [B, ...] tensor, got {tuple(getattr(depth, 'shape', ()))}")
+    B = depth.shape[0]
+    pd = _dev(depth, "depth", torch.float32)
+    po = _sized(who, "out", out, tuple(depth.shape), torch.float32)
+    pr = _sized(who, "range32", range32, (B, 2), torch.float32)
+    if out.device != depth.device or range32.device != depth.device:
+        raise HipExtError(f"{who}: depth on {depth.device}, out on {out.device}, range32 on {range32.device}")
+    lo, hi = (float(clip[0]), float(clip[1])) if clip is not None else (0.0, 0.0)
+    _check(load().ada_range_map_fwd(pd, pr, B, depth.numel() // B, float(scale), float(shift), int(clip is not None), lo, hi, po, _stream()), "ada_range_map_fwd")
+
+
+def depth_colorize(value, lut, out, range64=None, vmin=0.0, vmax=1.0, invalid_mask=None, invalid_val=-99.0, background=(128, 128, 128, 255)):
+    """value fp32 [B, h, w] -> out uint8 [B, h, w, 4]: the reference's colorize() below its percentiles (ada_depth_colorize_fwd).  The range is
+    ``range64`` (device fp64 [B, 2]) when given, else the host numbers vmin / vmax; ``lut`` uint8 [256, 4] R, G, B, A; invalid pixels (``invalid_mask``
+    uint8 [B, h, w] non-zero when given, else value == invalid_val) get ``background`` (R, G, B, A bytes).  All contiguous, one device."""
+    who = "depth_colorize"
+    if not isinstance(value, torch.Tensor) or value.dim() != 3 or not value.is_contiguous() or value.numel() == 0:
+        raise HipExtError(f"{who}: value must be a non-empty contiguous fp32 [B, h, w] tensor, got {tuple(getattr(value, 'shape', ()))}")
+    B, h, w = value.shape
+    pv = _dev(value, "value", torch.float32)
+    pl = _sized(who, "lut", lut, (256, 4), torch.uint8)
+    po = _sized(who, "out", out, (B, h, w, 4), torch.uint8)
+    pr = None if range64 is None else _sized(who, "range64", range64, (B, 2), torch.float64)
+    pm = None if invalid_mask is None else _sized(who, "invalid_mask", invalid_mask, (B, h, w), torch.uint8)
+    for name, t in (("lut", lut), ("out", out), ("range64", range64), ("invalid_mask", invalid_mask)):
+        if t is not None and t.device != value.device:
+            raise HipExtError(f"{who}: {name} on {t.device}, value on {value.device}")
+    r, g, b, a = (int(c) & 0xff for c in background)
+    _check(load().ada_depth_colorize_fwd(pv, B, h, w, pr, float(vmin), float(vmax), pl, pm, float(invalid_val), r | (g << 8) | (b << 16) | (a << 24), po,
+                                         _stream()), "ada_depth_colorize_fwd")
 
 
 # --- tuning / diagnostic hooks (include/ada_hip.h, last section) ---------------------------------

@@ -8,6 +8,9 @@ The two-model pipeline of infer.py prepares its photo differently (reference inf
 cv2's 8-bit INTER_LINEAR for the base network and torchvision's nearest for the amodal one, and nearest-resized masks.  photo_to_inputs,
 masks_to_tensor and resize_nearest do that on the device (ada_photo_prep_fwd, ada_mask_prep_fwd, ada_nearest_resize_fwd).
 
+colorize is the reference's depth-to-picture function (src/scripts/colorize_depth.py:18-84 and four more scripts): the 2nd / 95th percentile of the
+valid pixels (hip_ext.quantile, ada_quantile_fwd), the colour map and the background colour in one kernel (ada_depth_colorize_fwd), RGBA bytes out.
+
 render_depth is the other end of infer.py (reference infer.py:106-119): colour map, highlight_target, the nearest resize to the photo's size and the
 channel flip in one kernel (ada_depth_render_fwd), uint8 pixels out.  The outline it paints is the tree's stand-in (src/util/image_util.py
 draw_mask_outline), not cv2.findContours / drawContours: there is no cv2 here to pin those against.
@@ -19,7 +22,7 @@ import operator
 import numpy as np
 import torch
 
-from . import HipExtError, depth_render, depth_resize, image_prep, mask_prep, nearest_resize, photo_prep
+from . import HipExtError, depth_colorize, depth_render, depth_resize, image_prep, mask_prep, nearest_resize, photo_prep
 
 PIXEL_MEAN = (0.485, 0.456, 0.406)
 PIXEL_STD = (0.229, 0.224, 0.225)
@@ -206,6 +209,68 @@ def colormap_lut(cmap: str = "Spectral_r", device=None) -> torch.Tensor:
         table = (cm(np.arange(256))[:, :3] * 255).astype(np.uint8)
         _LUTS[key] = torch.from_numpy(np.ascontiguousarray(table)).to(device)
     return _LUTS[key]
+
+
+def colormap_lut_rgba(cmap: str = "turbo_r", device=None) -> torch.Tensor:
+    """The 256 colours of a matplotlib colour map as uint8 [256, 4] (R, G, B, A) on ``device``: cmap(arange(256), bytes=True), the table
+    ada_depth_colorize_fwd indexes.  Cached per (name, device); a map without 256 entries is refused, as by colormap_lut."""
+    import matplotlib
+    cm = matplotlib.colormaps[cmap]
+    if cm.N != 256:
+        raise ValueError(f"colormap_lut_rgba: colour map {cmap!r} has {cm.N} entries, the renderer needs 256")
+    device = torch.device(device) if device is not None else torch.device("cpu")
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (cmap, device, "rgba")
+    if key not in _LUTS:
+        _LUTS[key] = torch.from_numpy(np.ascontiguousarray(cm(np.arange(256), bytes=True))).to(device)
+    return _LUTS[key]
+
+
+def colorize(value, vmin=None, vmax=None, cmap="turbo_r", invalid_val=-99, invalid_mask=None, background_color=(128, 128, 128, 255), gamma_corrected=False,
+             value_transform=None, vminp=2, vmaxp=95):
+    """The reference's colorize() on the device: fp32 depth maps [B, H, W] (or one [H, W]) -> uint8 [B, H, W, 4] R, G, B, A on the device.  A bound left
+    None is its percentile (``vminp`` / ``vmaxp``) over the image's valid pixels -- those outside ``invalid_mask`` (uint8 / bool, non-zero = invalid) when
+    given, else those != ``invalid_val`` -- taken on the device (hip_ext.quantile.percentile_range); t = (value - vmin) / (vmax - vmin) in double
+    (value * 0 where the bounds are equal) through ``cmap`` as matplotlib's cmap(t, bytes=True); invalid pixels get ``background_color``.  The result is
+    the reference's on the map as float64.  Nothing is read back, the launches depend on the shape alone.  ``gamma_corrected`` and ``value_transform``
+    are not built."""
+    who = "colorize"
+    if gamma_corrected:
+        raise NotImplementedError(f"{who}: gamma_corrected is not built on the device (np.power(img / 255, 2.2) in double per byte; none of the reference's call sites sets it)")
+    if value_transform is not None:
+        raise NotImplementedError(f"{who}: value_transform is an arbitrary host callable on the normalised map; it cannot run inside the device kernel")
+    if not isinstance(value, torch.Tensor) or value.dtype != torch.float32 or value.dim() not in (2, 3) or value.numel() == 0:
+        raise HipExtError(f"{who}: expected fp32 [B, H, W] or [H, W], got {getattr(value, 'dtype', type(value).__name__)} {tuple(getattr(value, 'shape', ()))}")
+    if not value.is_cuda:
+        raise HipExtError(f"{who}: value on {value.device}, expected a HIP device (the HIP path has no CPU fallback)")
+    if value.dim() == 2:
+        value = value[None]
+        invalid_mask = invalid_mask[None] if isinstance(invalid_mask, torch.Tensor) and invalid_mask.dim() == 2 else invalid_mask
+    value = value.contiguous()
+    B, H, W = value.shape
+    dev = value.device
+    bg = tuple(_as_int(v) for v in background_color) if isinstance(background_color, (tuple, list)) and len(background_color) == 4 else (None,)
+    if None in bg or not all(0 <= v <= 255 for v in bg):
+        raise ValueError(f"{who}: background_color must be four bytes (R, G, B, A), got {background_color!r}")
+    mask = None
+    if invalid_mask is not None:
+        from .quantile import _as_mask
+        mask = _as_mask(invalid_mask, value, who, "invalid_mask")
+    range64 = None
+    if vmin is None or vmax is None:
+        from .quantile import percentile_range
+        range64, _ = percentile_range(value, vminp, vmaxp, invalid_val=invalid_val, invalid_mask=mask)
+        if vmin is not None:
+            range64[:, 0] = float(vmin)
+        if vmax is not None:
+            range64[:, 1] = float(vmax)
+    lut = colormap_lut_rgba(cmap, dev)
+    out = torch.empty(B, H, W, 4, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        depth_colorize(value, lut, out, range64=range64, vmin=0.0 if vmin is None else float(vmin), vmax=1.0 if vmax is None else float(vmax),
+                       invalid_mask=mask, invalid_val=float(invalid_val), background=bg)
+    return out
 
 
 def render_depth(depth, masks=None, out_size=None, cmap="Spectral_r", vmin=0.0, vmax=1.0, minmax=None, thickness=2, outline=(0, 0, 0), alpha=0.0,

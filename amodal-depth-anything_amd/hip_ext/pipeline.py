@@ -76,7 +76,7 @@ def fit_scale_shift(amodal: torch.Tensor, base: torch.Tensor, visible: torch.Ten
 
 @torch.no_grad()
 def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None, size: int = 518, out_size=None, check: bool = True,
-                       render: bool = False, min_area=None, min_area_connectivity: int = 4):
+                       render: bool = False, min_area=None, min_area_connectivity: int = 4, render_percentiles=None):
     """The reference's infer.py call on the device: a decoded uint8 BGR(A) photo [h, w, 3 | 4] and K amodal masks (uint8 / bool [h, w] or
     [K, h, w]) in, an AmodalResult out.  The base network runs once (B = 1), the amodal network once as a batch of K.
 
@@ -90,7 +90,9 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
     outline and overlay of highlight_target on the amodal ones, B, G, R), rendered from the network-size maps straight to out_size.
     min_area: when given, the AMODAL masks are first cleaned as given, at their own resolution, by hip_ext.masks.remove_small_noise (the demo's
     filter, app.py:283-293: components of fewer than min_area pixels under min_area_connectivity go) -- specks of a segmenter's mask would otherwise be
-    guidance for the network and receive pasted depth.  The visible masks are not touched.  None: nothing runs, the call is exactly the one without it."""
+    guidance for the network and receive pasted depth.  The visible masks are not touched.  None: nothing runs, the call is exactly the one without it.
+    render_percentiles: (lo, hi) in [0, 100] -- with render=True each picture is coloured between these percentiles of its own map (colorize()'s range,
+    hip_ext.quantile.percentile_range, taken on the device) instead of between 0 and 1.  None: the pictures are exactly the ones without it."""
     from .image import _as_int, _check_size, masks_to_tensor, photo_to_inputs, render_depth, resize_nearest
     size = _check_size(size, "amodal_infer_image")
     if not (out_size is None or (isinstance(out_size, str) and out_size == "image")
@@ -124,7 +126,12 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
         blend_ex(pred, base_k, m, blended, scale_shift)
         base_out = base_norm
         target = None if out_size is None else ((h, w) if out_size == "image" else tuple(out_size))
-        if render:
+        if render and render_percentiles is not None:
+            from .quantile import percentile_range
+            lo_p, hi_p = render_percentiles
+            raw_rendered = render_depth(base_norm, out_size=target, minmax=percentile_range(base_norm, lo_p, hi_p, invalid_val=None)[1])
+            amodal_rendered = render_depth(blended, m, out_size=target, minmax=percentile_range(blended, lo_p, hi_p, invalid_val=None)[1])
+        elif render:
             raw_rendered = render_depth(base_norm, out_size=target)
             amodal_rendered = render_depth(blended, m, out_size=target)
         if target is not None:

@@ -530,6 +530,58 @@ int ada_depth_render_fwd(const float* depth, int32_t batch, int32_t hi, int32_t 
                          int32_t ho, int32_t wo, int32_t bgr, uint8_t* out, uint16_t* out_u16, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Exact per-image quantiles, and the two maps that use them.  Additions under ABI 10: no existing signature or struct moves.
+ *
+ * ada_quantile_fwd replaces np.percentile(value[mask], vminp / vmaxp) of the reference's colorize() (src/scripts/colorize_depth.py:55-56, repeated in
+ * four more scripts) and torch.quantile(depth_linear[valid_mask], [q, 1 - q]) of ScaleShiftDepthNormalizer (src/util/depth_transform.py:81-84): exact
+ * order statistics of an fp32 map, selected by an 8-bit radix select on the floats' order-preserving keys (csrc/ada_quantile.hip), not sorted, not
+ * read back.  The launch sequence (a clear of the workspace, four passes, one finish) depends on (batch, n) alone: capturable.
+ *   x          fp32 [batch, n], contiguous; n < 2^31, batch <= 65535
+ *   population of image b: the elements with valid[b][e] != 0 (valid: uint8 [batch, n] or NULL = all), with ADA_Q_EXCLUDE_VALUE those != exclude_value
+ *              (compared in double, as ada_depth_colorize_fwd compares invalid_val; a NaN is not equal to it), with ADA_Q_POSITIVE_ONLY those > 0 (a NaN is not)
+ *   q          HOST double [nq], 1 <= nq <= ADA_QUANTILE_MAX_Q, each in [0, 1] (a percentile p is p / 100.0)
+ *   mode       s = the sorted population, cnt its size:
+ *     ADA_Q_NUMPY  numpy's 'linear' on the values promoted to double: v = (cnt - 1) * q, j = floor(v), g = v - j, a = s[j], b = s[min(j + 1, cnt - 1)],
+ *                  r = a + (b - a) * g, or b - (b - a) * (1 - g) where g >= 0.5; every operation in double, rounded on its own
+ *     ADA_Q_TORCH  torch.quantile on an FMA-capable CPU build (every x86-64 with AVX2, every aarch64): r = fp32(q) * fp32(cnt - 1), lo = s[floor(r)], hi = s[ceil(r)], w = r - floor(r), d = hi - lo in fp32;
+ *                  lo + w * d where w < 0.5, else hi - d * (1 - w), the product fused into the sum (ATen's lerp is an fmadd), 1 - w rounded on its own.
+ *                  ATen's DEFAULT capability on a host without FMA rounds the product first and differs in the last bit in about 3 % of draws
+ *   out        double [batch, nq];  out_f32  fp32 [batch, nq] or NULL: the same values rounded -- with nq = 2 the [batch, 2] range that
+ *              ada_normalize_fwd, ada_depth_render_fwd (minmax) and ada_range_map_fwd read;  count  int64 [batch] or NULL: the population's size
+ *   corners    a NaN inside the population makes every result of that image NaN (both references); an empty population gives NaN and count 0;
+ *              -0 and +0 are equal values, which sign comes out is unspecified
+ *   workspace  the caller's, 16-byte aligned, batch * ADA_QUANTILE_WS_BYTES_PER_IMAGE bytes; cleared by the call itself
+ * Workgroups take ADA_QUANTILE_CHUNK elements of one image.  Only integer atomics: the same bits on every run.
+ *
+ * ada_range_map_fwd is the scale-and-shift of ScaleShiftDepthNormalizer.__call__ (src/util/depth_transform.py:87-94):
+ *   out = ((d - lo) / (hi - lo)) * scale + shift, then with clip != 0 clamped to [clip_lo, clip_hi] (torch.clip: NaN stays NaN); lo = range[b][0],
+ *   hi = range[b][1] from a DEVICE fp32 [batch, 2]; fp32 throughout, in this order, every operation rounded (no FMA, IEEE division).  lo == hi gives
+ *   what IEEE gives (0 / 0 = NaN, x / 0 = +-inf): the reference does not guard it either.  d, out: fp32 [batch, n].
+ *
+ * ada_depth_colorize_fwd is colorize() itself (src/scripts/colorize_depth.py:18-84) below its percentiles, on the map promoted to double:
+ *   t = (value - vmin) / (vmax - vmin) in double; vmin, vmax = range[b][0], range[b][1] from a DEVICE double [batch, 2] (ada_quantile_fwd's out), or
+ *   the two HOST doubles when range == NULL;  t = value * 0 where vmin == vmax
+ *   colour = lut[min((int)(t * 256), 255)], t < 0 -> lut[0], t >= 1 -> lut[255], a NaN t -> (0, 0, 0, 0): matplotlib's cmap(t, bytes=True) with
+ *   lut = DEVICE uint8 [256][4] R, G, B, A = cmap(arange(256), bytes=True)
+ *   invalid pixels get background_rgba (R | G << 8 | B << 16 | A << 24): invalid_mask[b][pixel] != 0 (uint8 [batch, h, w]) when given, else
+ *   value == invalid_val, compared in double.  out: uint8 [batch, h, w, 4].
+ * ---------------------------------------------------------------------------------------- */
+#define ADA_Q_NUMPY 0
+#define ADA_Q_TORCH 1
+#define ADA_Q_EXCLUDE_VALUE 0x1
+#define ADA_Q_POSITIVE_ONLY 0x2
+#define ADA_QUANTILE_MAX_Q 4
+#define ADA_QUANTILE_CHUNK 4096
+#define ADA_QUANTILE_WS_BYTES_PER_IMAGE 33792   /* 4 passes x 8 ranks x 256 bins x 4 bytes + 1 KiB of rank state */
+int ada_quantile_fwd(const float* x, const uint8_t* valid, int32_t batch, int64_t n_per_image, const double* q, int32_t nq, int32_t mode,
+                     int32_t flags, double exclude_value, double* out, float* out_f32, int64_t* count, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int ada_range_map_fwd(const float* d, const float* range, int32_t batch, int64_t n_per_image, float scale, float shift, int32_t clip, float clip_lo,
+                      float clip_hi, float* out, void* stream);
+int ada_depth_colorize_fwd(const float* value, int32_t batch, int32_t h, int32_t w, const double* range, double vmin, double vmax,
+                           const uint8_t* lut, const uint8_t* invalid_mask, double invalid_val, uint32_t background_rgba, uint8_t* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The ADIW pseudo-label generator (reference src/scripts/sam_pl_gen_dav2.py), which prepares every photo and mask with Pillow on the host
  * (Image.open(fp).convert('RGB').resize((518, 518)), lines 28, 93-98) and quantises the label with numpy (lines 115-121).  Additions under ABI 10.
  *   ada_pil_resize_u8_fwd   Pillow's ImagingResample for 8-bit pixels with filter BICUBIC (libImaging/Resample.c), and its NEAREST, byte for byte.

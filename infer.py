@@ -9,12 +9,13 @@
     blend       : paste amodal depth inside the mask, 3x3 box-blur on the mask border             (infer.py:30-44)
     outputs     : {name}_raw_depth_rendered.png, {name}_amodal_depth_rendered.png                 (infer.py:118-119)
 
-Three opt-in flags go beyond the reference's CLI: --device_prep prepares the photo and the mask on the device too (hip_ext.pipeline.amodal_infer_image:
+Four opt-in flags go beyond the reference's CLI: --device_prep prepares the photo and the mask on the device too (hip_ext.pipeline.amodal_infer_image:
 cv2's 8-bit INTER_LINEAR restated from OpenCV's arithmetic instead of the float stand-in below, which can move the base network's input by one grey
 level), --visible_mask_path adds the alignment step of the reference's demo (app.py:214-216, 249-265), and --device_render (with --device_prep)
 renders the two pictures on the device as well (hip_ext.image.render_depth): only uint8 pixels come back, no depth map.  It is a flag of its own
 because its resize back to the photo's size follows cv2's INTER_NEAREST index rule, which the host helper resize_nearest does not for every pair
-of sizes.  Without them nothing changes.
+of sizes.  --render_percentiles LO HI (with --device_render) colours each picture between those percentiles of its own map, taken on the device
+(hip_ext.quantile.percentile_range; the reference's colorize() uses 2 and 95), instead of between 0 and 1.  Without them nothing changes.
 
 Differences forced by the environment: the reference hard-codes .cuda() and downloads weights from
 the HF hub; here --device selects the device, --amodal_weights / --raw_weights load local checkpoints, and without
@@ -129,16 +130,17 @@ def _device_prep_pipeline(image_bgr, amodal_mask, visible_mask, model_raw, depth
     return res.base.cpu(), res.blended[0].cpu(), (res.masks[0].cpu().numpy() > 0).astype(np.uint8) * 255
 
 
-def _device_render_pipeline(image_bgr, amodal_mask, visible_mask, model_raw, depth_amodal_model):
+def _device_render_pipeline(image_bgr, amodal_mask, visible_mask, model_raw, depth_amodal_model, render_percentiles=None):
     """--device_prep --device_render: as _device_prep_pipeline, and the colour map, the highlight, the resize to the photo's size and the channel flip
     run on the device too.  Returns the two uint8 B, G, R pictures [h, w, 3] on the host; no depth map is copied."""
     from hip_ext.pipeline import amodal_infer_image
-    res = amodal_infer_image(model_raw, depth_amodal_model, image_bgr, amodal_mask, visible_masks=visible_mask, size=518, out_size="image", render=True)
+    res = amodal_infer_image(model_raw, depth_amodal_model, image_bgr, amodal_mask, visible_masks=visible_mask, size=518, out_size="image", render=True,
+                             render_percentiles=render_percentiles)
     return res.raw_rendered.cpu().numpy(), res.amodal_rendered[0].cpu().numpy()
 
 
 def infer_single_image(input_image_path, input_mask_path, output_path, model_raw, depth_amodal_model, device="cuda", device_prep=False,
-                       visible_mask_path=None, device_render=False):
+                       visible_mask_path=None, device_render=False, render_percentiles=None):
     file_name = os.path.basename(input_image_path).split(".")[0]
     os.makedirs(output_path, exist_ok=True)
     image_bgr = imread_bgr(input_image_path)
@@ -147,13 +149,15 @@ def infer_single_image(input_image_path, input_mask_path, output_path, model_raw
         raise ValueError("--visible_mask_path needs --device_prep (the alignment is part of the on-device call)")
     if device_render and not device_prep:
         raise ValueError("--device_render needs --device_prep (the rendering is part of the on-device call)")
+    if render_percentiles is not None and not device_render:
+        raise ValueError("--render_percentiles needs --device_render (the percentiles are taken on the device)")
     if device_prep and not str(device).startswith("cuda"):
         raise ValueError("--device_prep needs a HIP device")
     if str(device).startswith("cuda"):
         amodal_mask = _read_mask(input_mask_path)
         if device_render:
             visible = _read_mask(visible_mask_path) if visible_mask_path is not None else None
-            raw_out, agg_out = _device_render_pipeline(image_bgr, amodal_mask, visible, model_raw, depth_amodal_model)
+            raw_out, agg_out = _device_render_pipeline(image_bgr, amodal_mask, visible, model_raw, depth_amodal_model, render_percentiles)
             imwrite_bgr(os.path.join(output_path, f"{file_name}_raw_depth_rendered.png"), raw_out)
             imwrite_bgr(os.path.join(output_path, f"{file_name}_amodal_depth_rendered.png"), agg_out)
             return raw_out, agg_out
@@ -216,11 +220,16 @@ if __name__ == "__main__":
                         help="mask of the object's visible part: fit the amodal depth to the base depth over it before blending (needs --device_prep)")
     parser.add_argument("--device_render", action="store_true",
                         help="render the two pictures on the device too: colour map, outline, cv2's nearest resize, channel flip (needs --device_prep)")
+    parser.add_argument("--render_percentiles", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                        help="colour each picture between these percentiles of its own map (the reference's colorize() uses 2 95) instead of 0..1 (needs --device_render)")
     args = parser.parse_args()
+    if args.render_percentiles is not None and not args.device_render:
+        parser.error("--render_percentiles needs --device_render")
     if args.visible_mask_path is not None and not args.device_prep:
         parser.error("--visible_mask_path needs --device_prep")
     if args.device_render and not args.device_prep:
         parser.error("--device_render needs --device_prep")
     m_raw, m_amodal = load_models(args.device, args.raw_weights, args.amodal_weights, args.raw_encoder, args.amodal_encoder)
     infer_single_image(args.input_image_path, args.input_mask_path, args.output_folder, m_raw, m_amodal, args.device,
-                       device_prep=args.device_prep, visible_mask_path=args.visible_mask_path, device_render=args.device_render)
+                       device_prep=args.device_prep, visible_mask_path=args.visible_mask_path, device_render=args.device_render,
+                       render_percentiles=None if args.render_percentiles is None else tuple(args.render_percentiles))
