@@ -162,7 +162,8 @@ ADA_DEV void epi_value(float4 (&v)[NV], const ColConst<NV>& c, const float4* r, 
 ADA_DEV float4 relu4_if(float4 v, bool on) { return on ? relu4(v) : v; }
 
 // Walks GEMM rows m, m+step, m+2*step ... through the interior of a zero-bordered [B, map_h+2, map_w+2] grid without a
-// division per row (valid for step <= map_w).
+// division per row.  pad_step wraps x ONCE: valid for step <= map_w only, and the step is the caller's rows-per-access (8 or 16 on the operand-only
+// path, 4 or 8 on the fp32 / residual path, by the tile's epilogue group width) -- the caller's map_w bound is that step, not a constant.
 struct PadWalk {
     int x, y;
     long prow;
@@ -653,6 +654,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4 && 
     // taken, and the "memory" clobbers of dump() then make every pass re-read the kernel arguments it uses (the row-map divisors alone 50 times in a
     // 128x64 kernel: +7 % instructions in the .s of every STD / GELU / SHUFFLE kernel).
     constexpr int CG4 = GW / 4, RPI4 = 64 / CG4, NKI = 32 / RPI4, NPASS = NG * TI;
+    constexpr int RPI8 = 512 / GW;   // rows per wave-wide access of the 8-column (operand-only) paths; with RPI4 the two PadWalk steps of this instantiation
     auto res_passes = [=](auto res_addr, auto begin, auto row) __attribute__((always_inline)) {
         constexpr bool AHEAD = (NWAVES == 8 && TJ <= 2) || PIPE4;
         const bool has_res = (flags & ADA_EP_RESIDUAL) != 0;
@@ -761,7 +763,10 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4 && 
             }
         }
     } else if (EPI != EPI_SHUFFLE && m0 + BM <= p.M && n0 + BN <= p.N && p.res_row_mod == 0 && p.bias_row_mod == 0 &&
-               (!p.out_op || p.map_op == ADA_MAP_PLAIN || (p.map_op == ADA_MAP_PAD && p.map_w >= 8)) &&
+               // (a padded map must be at least as wide as the PadWalk step of the half below that takes it: RPI8 on the operand-only half -- 16 on the
+               //  256x32 tile, whose 32-column groups used to send maps 8 ... 15 wide here and misplace every second store -- RPI4 on the other)
+               (!p.out_op || p.map_op == ADA_MAP_PLAIN ||
+                (p.map_op == ADA_MAP_PAD && p.map_w >= ((!p.out_f32 && !(flags & ADA_EP_RESIDUAL)) ? RPI8 : RPI4))) &&
                (!p.out_f32 || p.map_f32 == ADA_MAP_PLAIN) &&
                (p.out_f32 || (flags & ADA_EP_RESIDUAL) || (p.ldo_op & 7) == 0)) {
         // ---- interior tiles with plain (or zero-bordered NHWC) row maps -- every linear layer of the encoder, the 3x3 convs of
@@ -771,6 +776,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64, (WAVES_M * WAVES_N == 4 && 
         const bool has_gamma = (flags & ADA_EP_GAMMA) != 0;
         if (!p.out_f32 && !(flags & ADA_EP_RESIDUAL)) {
             constexpr int CG = GW / 8, RPI = 64 / CG;
+            static_assert(RPI == RPI8, "the branch condition bounds map_w by this walk's step");
             // Lane -> (slab row rsub, column group cg).  The slab reads are ds_read_b128, serviced in the lane groups {0-3, 12-15, 20-27},
             // {4-11, 16-19, 28-31}, ... (MI355X_MICROARCH.md, LDS): with cg = lane % CG two lanes of every group met on one 16-byte bank slot
             // (rows are SW = GW + 4 floats apart), i.e. every read took twice its LDS cycles -- 4-6 % of ALL LDS cycles of the kernel
