@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)     # isa_guard.py lives next to this file: the package builds without the repository's tools/
-SOURCES = ["ada_api.hip", "ada_igemm.hip", "ada_attention.hip", "ada_elementwise.hip", "ada_pipeline.hip", "ada_eval.hip", "ada_tail.hip", "ada_image.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip"]
+SOURCES = ["ada_api.hip", "ada_igemm.hip", "ada_attention.hip", "ada_elementwise.hip", "ada_pipeline.hip", "ada_eval.hip", "ada_tail.hip", "ada_image.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip"]
 HEADERS = ["ada_common.h", "ada_igemm_pipe4.inc", os.path.join("..", "..", "include", "ada_hip.h")]
 ARCH = "gfx950"
 # ada_tail.hip: no SLP vectorisation.  Vectorised, the producers' interpolation becomes v_pk_mul_f32 / v_pk_fma_f32 on register pairs
@@ -27,7 +27,9 @@ ARCH = "gfx950"
 # files (attention, LayerNorm, resizes) the vectoriser helps or is neutral -- attention is 1 % slower without it.
 # (-Wno-inline-asm: the generated loop lists m0 among its clobbers -- it rewrites m0 for its LDS-DMA copies and the backend's merging of
 # identical m0 initialisations must see that -- and clang warns about every reserved register in a clobber list.)
-PER_FILE_FLAGS = {"ada_tail.hip": ["-fno-slp-vectorize"], "ada_igemm.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"]}
+# ada_geometry.hip: no contraction.  Its fp64 unprojection reproduces numpy's bits only when every product and every sum is rounded on its own; the
+# kernel spells that with __dmul_rn / __dadd_rn, and the flag keeps a later edit in plain operators from turning into FMAs unnoticed.
+PER_FILE_FLAGS = {"ada_tail.hip": ["-fno-slp-vectorize"], "ada_igemm.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"], "ada_geometry.hip": ["-ffp-contract=off"]}
 # ada_igemm.hip joined in round 4: a by-reference lambda capture of the k-walk counters put them into scratch behind the loop's "memory"-clobbering
 # waits -- 12 bytes reloaded every k-step of every GEMM, silently, for most of a round.  No kernel of these files may use scratch or spill VGPRs.
 # ada_image.hip / ada_pipeline.hip hold no hand-managed loads: their kernels are single memory-bound passes, one thread per output pixel, where any
@@ -40,7 +42,9 @@ PER_FILE_FLAGS = {"ada_tail.hip": ["-fno-slp-vectorize"], "ada_igemm.hip": ["-fn
 # run in registers; a per-thread array or a by-reference capture there would turn every step of a chase into a scratch access.
 # ada_quantile.hip: a thread holds its 16 elements of the chunk in arrays indexed by unrolled constants (the loads go out before any bin is touched);
 # the per-rank state is indexed at run time and therefore lives in LDS, never in a per-thread array.
-NO_SCRATCH = {"ada_tail.hip", "ada_igemm.hip", "ada_image.hip", "ada_pipeline.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip"}
+# ada_geometry.hip: the unprojection keeps a pixel's nine fp64 products and the predicate a cell's four depths in arrays indexed by unrolled constants,
+# and the camera's 21 doubles arrive in the kernel-argument struct (scalar loads); one runtime index into any of them would move it to scratch.
+NO_SCRATCH = {"ada_tail.hip", "ada_igemm.hip", "ada_image.hip", "ada_pipeline.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip"}
 # Round 4: the wrong results above were root-caused (profiles/r04_a_tail_inflight_register_root_cause.txt) -- NOT a hardware hazard of packed
 # fp32 beside MFMAs (tools/ubench/pk_f32_beside_mfma.hip: 0 mismatches) but the compiler copying registers that the kernel's inline-asm
 # fetches were still writing: with SLP on, the allocator parks a source row in other registers with v_mov_b64 placed ABOVE the hand-counted

@@ -34,6 +34,7 @@ EXPORTS = (
     "ada_pil_resize_u8_fwd", "ada_label_combine_fwd",
     "ada_mask_label_fwd", "ada_mask_stats_fwd", "ada_mask_keep_area_fwd", "ada_mask_grid_points_fwd",
     "ada_quantile_fwd", "ada_range_map_fwd", "ada_depth_colorize_fwd",
+    "ada_depth_points_fwd", "ada_mesh_triangles_fwd", "ada_mesh_compact_fwd",
     "ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_last_tile",
     "ada_debug_set_timestamps", "ada_debug_set_attention_variant", "ada_debug_count_saturated",
 )
@@ -56,6 +57,10 @@ Q_EXCLUDE_VALUE, Q_POSITIVE_ONLY = 0x1, 0x2
 QUANTILE_MAX_Q = 4
 QUANTILE_CHUNK = 4096
 QUANTILE_WS_BYTES_PER_IMAGE = 33792
+# ada_mesh_triangles_fwd / ada_mesh_compact_fwd: candidates per ballot, cells or vertices per workgroup, workgroup sums per step of the scan
+GEOM_WAVE = 64
+GEOM_CHUNK = 1024
+GEOM_SCAN_BLOCK = 1024
 
 
 class IgemmArgs(ctypes.Structure):
@@ -208,6 +213,15 @@ def load(path: Optional[str] = None):
     lib.ada_depth_colorize_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_double, c_double, c_void_p, c_void_p, c_double, ctypes.c_uint32,
                                            c_void_p, c_void_p]
     lib.ada_depth_colorize_fwd.restype = c_int
+    lib.ada_depth_points_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, ctypes.POINTER(c_double), c_int32, c_double, c_double, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]
+    lib.ada_depth_points_fwd.restype = c_int
+    lib.ada_mesh_triangles_fwd.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_double, c_double, c_double, c_int32, c_int32, c_int32, c_void_p,
+                                           c_int32, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.ada_mesh_triangles_fwd.restype = c_int
+    lib.ada_mesh_compact_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
+                                         c_void_p, c_void_p, c_int64, c_void_p]
+    lib.ada_mesh_compact_fwd.restype = c_int
     for name in ("ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_set_attention_variant"):
         getattr(lib, name).argtypes = [c_int]
         getattr(lib, name).restype = None
@@ -815,6 +829,96 @@ def quantile_select(x, q, out, out_f32=None, count=None, valid=None, mode=Q_NUMP
     ws, ws_bytes = _bytes_of(who, workspace, quantile_workspace_bytes(B), x.device)
     _check(load().ada_quantile_fwd(px, pv, B, n, (c_double * nq)(*qs), nq, int(mode), int(flags), float(exclude_value), po, pf, pc, ws.data_ptr(), ws_bytes,
                                    _stream()), "ada_quantile_fwd")
+
+
+def mesh_triangles_workspace_bytes(batch: int, h: int, w: int) -> int:
+    """Bytes of workspace ada_mesh_triangles_fwd asks for (include/ada_hip.h)."""
+    return 4 * batch * max(1, ((h - 1) * (w - 1) + GEOM_CHUNK - 1) // GEOM_CHUNK)
+
+
+def mesh_compact_workspace_bytes(batch: int, h: int, w: int) -> int:
+    """Bytes of workspace ada_mesh_compact_fwd asks for (include/ada_hip.h)."""
+    return 4 * batch * (h * w + (h * w + GEOM_CHUNK - 1) // GEOM_CHUNK)
+
+
+def _depth_maps(who, depth):
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 3 or not depth.is_contiguous():
+        raise HipExtError(f"{who}: depth must be a contiguous fp32 [B, h, w] tensor, got {tuple(getattr(depth, 'shape', ()))}")
+    _dev(depth, "depth", torch.float32)
+    return tuple(depth.shape)
+
+
+def _z_rule(inverse):
+    return (0, 0.0, 0.0) if inverse is None else (1, float(inverse[0]), float(inverse[1]))
+
+
+def depth_points(depth, camera, out_f64=None, out_f32=None, valid=None, inverse=None):
+    """depth fp32 [B, h, w] -> points [B, h, w, 3] as fp64 and / or fp32 and optionally valid uint8 [B, h, w] (ada_depth_points_fwd).  ``camera``: 21
+    host doubles, Kinv row-major, R row-major, t.  ``inverse``: None for z = depth, (a, b) for z = 1 / (a depth + b)."""
+    who = "depth_points"
+    B, h, w = _depth_maps(who, depth)
+    cam = [float(v) for v in camera]
+    if len(cam) != 21:
+        raise HipExtError(f"{who}: camera must hold 21 doubles (Kinv, R, t), got {len(cam)}")
+    if out_f64 is None and out_f32 is None:
+        raise HipExtError(f"{who}: one of out_f64 / out_f32 is needed")
+    p64 = None if out_f64 is None else _sized(who, "out_f64", out_f64, (B, h, w, 3), torch.float64)
+    p32 = None if out_f32 is None else _sized(who, "out_f32", out_f32, (B, h, w, 3), torch.float32)
+    pv = None if valid is None else _sized(who, "valid", valid, (B, h, w), torch.uint8)
+    inv, a, b = _z_rule(inverse)
+    _check(load().ada_depth_points_fwd(depth.data_ptr(), B, h, w, (c_double * 21)(*cam), inv, a, b, p64, p32, pv, _stream()), "ada_depth_points_fwd")
+
+
+def mesh_triangles(batch, h, w, triangles, count, mask=None, row_pitch=0, image_stride=0, depth=None, inverse=None, max_ratio=0.0, workspace=None):
+    """The kept triangles of create_triangles's candidate list, in its order (ada_mesh_triangles_fwd): triangles int32 [batch, capacity, 3] receives the
+    first min(count, capacity) of each image, count int32 [batch] the true number.  ``mask``: uint8, rows ``row_pitch`` bytes and images ``image_stride``
+    bytes apart (non-zero = inside) or None; ``depth``: contiguous fp32 [batch, h, w] or None, with ``inverse`` as in depth_points; ``max_ratio`` <= 0: off.
+    ``workspace``: any contiguous device tensor of at least mesh_triangles_workspace_bytes(batch, h, w) bytes, allocated when None."""
+    who = "mesh_triangles"
+    if not isinstance(triangles, torch.Tensor) or triangles.dim() != 3 or triangles.shape[0] != batch or triangles.shape[2] != 3 or not triangles.is_contiguous():
+        raise HipExtError(f"{who}: triangles must be a contiguous int32 [{batch}, capacity, 3] tensor, got {tuple(getattr(triangles, 'shape', ()))}")
+    pt = _dev(triangles, "triangles", torch.int32)
+    pc = _sized(who, "count", count, (batch,), torch.int32)
+    pm = None
+    if mask is not None:
+        pm = _dev(mask, "mask", torch.uint8)
+        _check_src_extent(who, mask, (batch - 1) * image_stride + (h - 1) * row_pitch + w)
+    pd = None
+    if depth is not None:
+        if _depth_maps(who, depth) != (batch, h, w):
+            raise HipExtError(f"{who}: depth must be [{batch}, {h}, {w}], got {tuple(depth.shape)}")
+        pd = depth.data_ptr()
+    inv, a, b = _z_rule(inverse)
+    ws, ws_bytes = _bytes_of(who, workspace, mesh_triangles_workspace_bytes(batch, h, w), triangles.device)
+    _check(load().ada_mesh_triangles_fwd(pm, int(row_pitch), int(image_stride), pd, inv, a, b, float(max_ratio), batch, h, w, pt, triangles.shape[1], pc,
+                                         ws.data_ptr(), ws_bytes, _stream()), "ada_mesh_triangles_fwd")
+
+
+def mesh_compact(triangles, count, h, w, points, points_out, vertex_count, colors=None, colors_out=None, workspace=None):
+    """The vertices that the first min(count, capacity) triangles of each image use, in raster order (ada_mesh_compact_fwd): points [B, h * w, 3] (fp32 or
+    fp64) -> points_out [B, vertex_capacity, 3], colors uint8 [B, h * w, 3] -> colors_out likewise, vertex_count int32 [B]; triangles int32
+    [B, capacity, 3] is rewritten in place to the new numbering.  ``workspace``: at least mesh_compact_workspace_bytes(B, h, w) bytes, allocated when None."""
+    who = "mesh_compact"
+    if not isinstance(triangles, torch.Tensor) or triangles.dim() != 3 or triangles.shape[2] != 3 or not triangles.is_contiguous():
+        raise HipExtError(f"{who}: triangles must be a contiguous int32 [B, capacity, 3] tensor, got {tuple(getattr(triangles, 'shape', ()))}")
+    B, cap = triangles.shape[0], triangles.shape[1]
+    pt = _dev(triangles, "triangles", torch.int32)
+    pc = _sized(who, "count", count, (B,), torch.int32)
+    if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64):
+        raise HipExtError(f"{who}: points must be an fp32 or fp64 tensor")
+    pp = _sized(who, "points", points, (B, h * w, 3), points.dtype)
+    if not isinstance(points_out, torch.Tensor) or points_out.dim() != 3:
+        raise HipExtError(f"{who}: points_out must be a [B, vertex_capacity, 3] tensor")
+    vcap = points_out.shape[1]
+    po = _sized(who, "points_out", points_out, (B, vcap, 3), points.dtype)
+    pv = _sized(who, "vertex_count", vertex_count, (B,), torch.int32)
+    if (colors is None) != (colors_out is None):
+        raise HipExtError(f"{who}: colors and colors_out come together")
+    pci = None if colors is None else _sized(who, "colors", colors, (B, h * w, 3), torch.uint8)
+    pco = None if colors_out is None else _sized(who, "colors_out", colors_out, (B, vcap, 3), torch.uint8)
+    ws, ws_bytes = _bytes_of(who, workspace, mesh_compact_workspace_bytes(B, h, w), triangles.device)
+    _check(load().ada_mesh_compact_fwd(pt, pc, cap, B, h, w, pp, points.element_size(), pci, po, pco, vcap, pv, ws.data_ptr(), ws_bytes, _stream()),
+           "ada_mesh_compact_fwd")
 
 
 def range_map(depth, range32, out, scale=1.0, shift=0.0, clip=None):

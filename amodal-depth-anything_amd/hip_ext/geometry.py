@@ -1,0 +1,365 @@
+"""Depth maps to geometry on the device: what the reference does on the host in numpy (src/models/amodalsynthdrive/zoedepth/utils/geometry.py:
+get_intrinsics, depth_to_points, create_triangles) with the maps left in HBM (csrc/ada_geometry.hip), up to the layered meshes of an amodal result.
+
+Exact against the reference: the points of the default pose (R = None, t = None) for any pinhole K without skew, bit for bit in float64, and the
+triangle list, order included (int32 here, int64 there).  A general pose differs from numpy's stacked matmul in the last ulps, within
+2 gamma_4 (sum_j |R_ij| |q_j| + |t_i|) (include/ada_hip.h).  This library's own: the inverse-depth mode z = 1 / (a depth + b), vertex validity
+(z finite and > 0), the ratio rule z_max <= max_ratio z_min of a kept triangle, the vertex compaction, and zero triangles for a grid one pixel wide
+with a mask (the reference raises there).
+
+Depth maps are fp32, [h, w] or [B, h, w], numpy arrays (copied to the device) or device tensors; masks are uint8 or bool as hip_ext.masks takes them
+(a pitched crop of a larger tensor is read in place).  There is no CPU fallback: a CPU tensor or a non-HIP target raises HipExtError.
+"""
+from __future__ import annotations
+
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import HipExtError, depth_points, mesh_compact, mesh_triangles
+from .image import _as_int
+
+Mesh = namedtuple("Mesh", "points triangles vertex_count triangle_count colors")
+Mesh.__doc__ = """One image's mesh on the device: points [vertex_count, 3] (fp32 or fp64), triangles int32 [triangle_count, 3] indexing them, the two counts as
+Python ints, colors uint8 [vertex_count, 3] (R, G, B) or None."""
+
+Layers = namedtuple("Layers", "scene objects")
+Layers.__doc__ = """amodal_layers: the scene Mesh (the base depth over every pixel) and a list of K object Meshes (each blended map over its amodal mask)."""
+
+MAX_PIXELS = 2 ** 30
+
+
+def get_intrinsics(h, w, fov_deg=55.0) -> np.ndarray:
+    """The reference's pinhole camera as a float64 3 x 3: focal length 0.5 w / tan(fov / 2) on both axes, principal point (w / 2, h / 2)."""
+    f = 0.5 * w / np.tan(0.5 * fov_deg * np.pi / 180.0)
+    return np.array([[f, 0.0, 0.5 * w], [0.0, f, 0.5 * h], [0.0, 0.0, 1.0]], dtype=np.float64)
+
+
+def _grid(who, h, w):
+    hw = _as_int(h), _as_int(w)
+    if None in hw or min(hw) < 1:
+        raise ValueError(f"{who}: h and w must be positive integers, got {h!r} x {w!r}")
+    if hw[0] * hw[1] >= MAX_PIXELS:
+        raise ValueError(f"{who}: h * w must stay below 2^30, got {hw[0]} x {hw[1]}")
+    return hw
+
+
+def _device_of(who, device, *arrays):
+    for a in arrays:
+        if device is None and isinstance(a, torch.Tensor):
+            device = a.device
+    if device is None and torch.cuda.is_available():
+        device = torch.device("cuda", torch.cuda.current_device())
+    device = torch.device(device) if device is not None else None
+    if device is None or device.type != "cuda":
+        raise HipExtError(f"{who}: target device {device} is not a HIP device (the HIP path has no CPU fallback)")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+def _check_depth(who, depth):
+    """Shape and type of a depth argument, before any device is looked at: (h, w, was_2d)."""
+    if isinstance(depth, np.ndarray):
+        ok = depth.dtype == np.float32
+    elif isinstance(depth, torch.Tensor):
+        ok = depth.dtype == torch.float32
+    else:
+        raise TypeError(f"{who}: depth must be a numpy array or a torch tensor, got {type(depth).__name__}")
+    if not ok:
+        raise TypeError(f"{who}: depth must be float32, got {depth.dtype}")
+    if depth.ndim not in (2, 3) or min(depth.shape) < 1:
+        raise ValueError(f"{who}: depth must be [h, w] or [B, h, w], got shape {tuple(depth.shape)}")
+    h, w = _grid(who, depth.shape[-2], depth.shape[-1])
+    if depth.ndim == 3 and depth.shape[0] > 65535:
+        raise ValueError(f"{who}: at most 65535 maps per call, got {depth.shape[0]}")
+    return h, w, depth.ndim == 2
+
+
+def _from_numpy(a):
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a if a.flags.writeable else a.copy())      # a decoded image is a read-only view; the tensor only feeds a copy to the device
+
+
+def _stage_depth(who, depth, device):
+    if isinstance(depth, np.ndarray):
+        d = _from_numpy(depth).to(device)
+    else:
+        if depth.device != device:
+            raise HipExtError(f"{who}: depth on {depth.device}, expected it on the HIP device {device}")
+        d = depth.contiguous()
+    return d[None] if d.dim() == 2 else d
+
+
+def _check_mask(who, mask):
+    if isinstance(mask, np.ndarray):
+        ok = mask.dtype in (np.uint8, np.bool_)
+    elif isinstance(mask, torch.Tensor):
+        ok = mask.dtype in (torch.uint8, torch.bool)
+    else:
+        raise TypeError(f"{who}: mask must be a numpy array or a torch tensor, got {type(mask).__name__}")
+    if not ok:
+        raise TypeError(f"{who}: mask must be uint8 or bool, got {mask.dtype}")
+    if mask.ndim not in (2, 3) or min(mask.shape) < 1:
+        raise ValueError(f"{who}: mask must be [h, w] or [B, h, w], got shape {tuple(mask.shape)}")
+    if mask.ndim == 3 and mask.shape[0] > 65535:
+        raise ValueError(f"{who}: at most 65535 masks per call, got {mask.shape[0]}")
+    return mask.ndim == 2
+
+
+def _stage_mask(who, mask, device):
+    """uint8 device tensor [B, h, w] whose rows are packed and whose pitches the kernel can walk: a crop stays a view."""
+    if isinstance(mask, np.ndarray):
+        m = torch.from_numpy(np.ascontiguousarray(mask).view(np.uint8).copy()).to(device)
+    else:
+        if mask.device != device:
+            raise HipExtError(f"{who}: mask on {mask.device}, expected it on the HIP device {device}")
+        m = mask
+    if m.dim() == 2:
+        m = m[None]
+    B, h, w = m.shape
+    if not (m.stride(2) == 1 and m.stride(1) >= w and (B == 1 or m.stride(0) >= (h - 1) * m.stride(1) + w)):
+        m = m.contiguous()
+    return m.view(torch.uint8) if m.dtype == torch.bool else m
+
+
+def _camera(who, h, w, R, t, K, fov_deg):
+    K = get_intrinsics(h, w, fov_deg) if K is None else np.asarray(K, dtype=np.float64)
+    R = np.eye(3) if R is None else np.asarray(R, dtype=np.float64)
+    t = np.zeros(3) if t is None else np.asarray(t, dtype=np.float64).reshape(-1)
+    if K.shape != (3, 3) or R.shape != (3, 3) or t.shape != (3,):
+        raise ValueError(f"{who}: K and R must be 3 x 3 and t must hold 3 values, got {K.shape}, {R.shape}, {t.shape}")
+    return list(np.linalg.inv(K).reshape(-1)) + list(R.reshape(-1)) + list(t)
+
+
+def _inverse(who, inverse):
+    if inverse is None:
+        return None
+    try:
+        a, b = (float(v) for v in inverse)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: inverse must be None or a pair (a, b), got {inverse!r}") from None
+    return a, b
+
+
+def _ratio(who, max_ratio, depth):
+    if max_ratio is None:
+        return 0.0
+    r = float(max_ratio)
+    if r != r:
+        raise ValueError(f"{who}: max_ratio is NaN")
+    if r > 0 and depth is None:
+        raise ValueError(f"{who}: max_ratio needs the depth map")
+    return r
+
+
+@torch.no_grad()
+def depth_to_points(depth, R=None, t=None, K=None, fov_deg=55.0, inverse=None, dtype=torch.float64, return_valid=False, device=None):
+    """The reference's depth_to_points on the device: depth fp32 [h, w] or [B, h, w] -> points [h, w, 3] / [B, h, w, 3] of ``dtype`` (torch.float64, the
+    reference's, or torch.float32 = the float64 result rounded once).  K defaults to get_intrinsics(h, w, fov_deg); its inverse is taken with
+    np.linalg.inv in float64, as the reference takes it.  ``inverse=(a, b)``: z = 1 / (a depth + b) instead of z = depth.  A vertex whose z is not finite
+    is NaN in all three coordinates; ``return_valid=True`` also returns uint8 [.., h, w], 1 where z is finite and > 0.  Nothing is read back."""
+    who = "depth_to_points"
+    h, w, was2d = _check_depth(who, depth)
+    if dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"{who}: dtype must be torch.float64 or torch.float32, got {dtype!r}")
+    cam = _camera(who, h, w, R, t, K, fov_deg)
+    inverse = _inverse(who, inverse)
+    device = _device_of(who, device, depth)
+    with torch.cuda.device(device):
+        d = _stage_depth(who, depth, device)
+        out = torch.empty(d.shape + (3,), dtype=dtype, device=device)
+        valid = torch.empty(d.shape, dtype=torch.uint8, device=device) if return_valid else None
+        depth_points(d, cam, out_f64=out if dtype == torch.float64 else None, out_f32=out if dtype == torch.float32 else None, valid=valid, inverse=inverse)
+    if was2d:
+        out, valid = out[0], (valid[0] if return_valid else None)
+    return (out, valid) if return_valid else out
+
+
+def _triangles(B, h, w, m, d, inverse, ratio, capacity, device):
+    tri = torch.empty(B, capacity, 3, dtype=torch.int32, device=device)
+    count = torch.empty(B, dtype=torch.int32, device=device)
+    mesh_triangles(B, h, w, tri, count, mask=m, row_pitch=0 if m is None else m.stride(1), image_stride=0 if m is None else m.stride(0), depth=d,
+                   inverse=inverse, max_ratio=ratio)
+    return tri, count
+
+
+@torch.no_grad()
+def create_triangles(h, w, mask=None, depth=None, inverse=None, max_ratio=None, capacity=None, device=None):
+    """The reference's create_triangles on the device: of the two triangles per pixel cell, (tl, bl, tr) then (br, tr, bl) in raster order, those whose
+    three vertices are all inside ``mask`` (None: every vertex).  With ``depth`` (fp32, the mask's shape) the three must also be valid vertices
+    (z finite and > 0, ``inverse`` as in depth_to_points), and with ``max_ratio`` > 0 additionally z_max <= max_ratio z_min -- this library's cut
+    of the sheet of stretched triangles that would join an occluder to what lies behind it.  A grid one pixel wide has no triangle.
+
+    ``capacity=None``: the counts are read back once (the one host read) and the result is a list of exactly sized int32 [n_b, 3] device tensors, or
+    one tensor when the mask (or, without one, the depth) is 2-D or both are None.  An explicit ``capacity``: (triangles int32 [B, capacity, 3],
+    count int32 [B]) with no host read; the first min(count, capacity) rows are filled and count > capacity is how the caller sees an overflow."""
+    who = "create_triangles"
+    h, w = _grid(who, h, w)
+    cap = None
+    if capacity is not None:
+        cap = _as_int(capacity)
+        if cap is None or cap < 0 or cap >= 2 ** 31:
+            raise ValueError(f"{who}: capacity must be an integer >= 0, got {capacity!r}")
+    single = True
+    if mask is not None:
+        single = _check_mask(who, mask)
+        if tuple(mask.shape[-2:]) != (h, w):
+            raise ValueError(f"{who}: mask of shape {tuple(mask.shape)} for a {h} x {w} grid")
+    if depth is not None:
+        dh, dw, d2 = _check_depth(who, depth)
+        if (dh, dw) != (h, w):
+            raise ValueError(f"{who}: depth of shape {tuple(depth.shape)} for a {h} x {w} grid")
+        if mask is None:
+            single = d2
+        elif d2 != single or (not d2 and depth.shape[0] != mask.shape[0]):
+            raise ValueError(f"{who}: mask {tuple(mask.shape)} and depth {tuple(depth.shape)} differ in shape")
+    inverse = _inverse(who, inverse)
+    ratio = _ratio(who, max_ratio, depth)
+    device = _device_of(who, device, mask, depth)
+    with torch.cuda.device(device):
+        m = None if mask is None else _stage_mask(who, mask, device)
+        d = None if depth is None else _stage_depth(who, depth, device)
+        B = m.shape[0] if m is not None else d.shape[0] if d is not None else 1
+        if cap is not None:
+            return _triangles(B, h, w, m, d, inverse, ratio, cap, device)
+        counts = _triangles(B, h, w, m, d, inverse, ratio, 0, device)[1].tolist()      # the one host read
+        tri = _triangles(B, h, w, m, d, inverse, ratio, max(counts), device)[0]
+        out = [tri[b, :n] for b, n in enumerate(counts)]
+    return out[0] if single else out
+
+
+def _stage_colors(who, colors, h, w, device):
+    if colors is None:
+        return None
+    if isinstance(colors, np.ndarray):
+        colors = _from_numpy(colors).to(device)
+    if not isinstance(colors, torch.Tensor) or colors.dtype != torch.uint8 or tuple(colors.shape) != (h, w, 3):
+        raise ValueError(f"{who}: colors must be uint8 [{h}, {w}, 3], got {getattr(colors, 'dtype', type(colors).__name__)} {tuple(getattr(colors, 'shape', ()))}")
+    if colors.device != device:
+        raise HipExtError(f"{who}: colors on {colors.device}, expected them on the HIP device {device}")
+    return colors.contiguous().reshape(1, h * w, 3)
+
+
+@torch.no_grad()
+def depth_to_mesh(depth, mask=None, colors=None, compact=True, R=None, t=None, K=None, fov_deg=55.0, inverse=None, max_ratio=None,
+                  dtype=torch.float32, device=None) -> Mesh:
+    """One depth map fp32 [h, w] -> a Mesh: depth_to_points, then create_triangles over ``mask`` (uint8 / bool [h, w] or None) with the validity and ratio
+    rules applied from the same map.  ``colors``: uint8 [h, w, 3] per vertex, or None.  ``compact=True`` keeps only the vertices a triangle uses, in
+    raster order, and renumbers the triangles; False keeps all h w points (invalid ones NaN or behind the camera, used by no triangle).
+    Host reads: the triangle count, and with compact the vertex count."""
+    who = "depth_to_mesh"
+    h, w, was2d = _check_depth(who, depth)
+    if not was2d:
+        raise ValueError(f"{who}: one map [h, w] per call, got shape {tuple(depth.shape)}")
+    if mask is not None and (not _check_mask(who, mask) or tuple(mask.shape) != (h, w)):
+        raise ValueError(f"{who}: mask must be [{h}, {w}], got shape {tuple(mask.shape)}")
+    device = _device_of(who, device, depth, mask)
+    with torch.cuda.device(device):
+        d = _stage_depth(who, depth, device)[0]
+        col = _stage_colors(who, colors, h, w, device)
+        points = depth_to_points(d, R=R, t=t, K=K, fov_deg=fov_deg, inverse=inverse, dtype=dtype, device=device).reshape(1, h * w, 3)
+        tri = create_triangles(h, w, mask=mask, depth=d, inverse=inverse, max_ratio=max_ratio, device=device)
+        n_tri = tri.shape[0]
+        if not compact:
+            return Mesh(points[0], tri, h * w, n_tri, None if col is None else col[0])
+        tri = tri.contiguous()[None]
+        count = torch.full((1,), n_tri, dtype=torch.int32, device=device)
+        vcap = min(h * w, 3 * n_tri)
+        p_out = torch.empty(1, vcap, 3, dtype=dtype, device=device)
+        c_out = None if col is None else torch.empty(1, vcap, 3, dtype=torch.uint8, device=device)
+        v_count = torch.empty(1, dtype=torch.int32, device=device)
+        mesh_compact(tri, count, h, w, points, p_out, v_count, colors=col, colors_out=c_out)
+        n_v = int(v_count.item())
+    return Mesh(p_out[0, :n_v], tri[0], n_v, n_tri, None if c_out is None else c_out[0, :n_v])
+
+
+@torch.no_grad()
+def amodal_layers(result, image=None, near=1.0, far=10.0, fov_deg=55.0, max_ratio=None) -> Layers:
+    """The layered geometry of an AmodalResult (hip_ext.pipeline.amodal_infer_image): the scene Mesh from ``result.base`` over every pixel and one Mesh per
+    object from ``result.blended[k]`` over ``result.masks[k] > 0`` -- the occluded object reconstructed behind its occluder.
+
+    The maps are normalised inverse depth in [0, 1]; this library's choice of metric is z = 1 / (a v + b) with a = 1 / near - 1 / far, b = 1 / far:
+    v = 1 lies at ``near``, v = 0 at ``far``.  The reference fixes no such mapping.  With far = inf the pixel at v = 0 (``base`` contains one exactly) has
+    no finite z: it is an invalid vertex and belongs to no triangle.  ``image``: the photo, uint8 [h, w, 3] in B, G, R order, brought to the maps' size by
+    hip_ext.image.resize_nearest's rule, gives the vertex colours (stored R, G, B).  An all-zero mask gives an empty Mesh.  base and blended must have one
+    size (call amodal_infer_image with the same out_size for both, its default)."""
+    who = "amodal_layers"
+    base, blended, masks = result.base, result.blended, result.masks
+    for name, v in (("base", base), ("blended", blended), ("masks", masks)):
+        if not isinstance(v, torch.Tensor) or not v.is_cuda:
+            raise HipExtError(f"{who}: result.{name} must be a tensor on a HIP device (the HIP path has no CPU fallback)")
+    if base.dim() != 2 or blended.dim() != 3 or tuple(blended.shape[1:]) != tuple(base.shape):
+        raise ValueError(f"{who}: base [h, w] and blended [K, h, w] of one size expected, got {tuple(base.shape)} and {tuple(blended.shape)}")
+    h, w = base.shape
+    if not (near > 0 and far > near):
+        raise ValueError(f"{who}: 0 < near < far expected, got near={near!r} far={far!r}")
+    inverse = (1.0 / near - 1.0 / far, 1.0 / far)
+    with torch.cuda.device(base.device):
+        if tuple(masks.shape[1:]) != (h, w):
+            from .image import resize_nearest
+            masks = resize_nearest(masks.float().contiguous(), h, w)
+        colors = None
+        if image is not None:
+            from .image import resize_nearest
+            img = _from_numpy(image) if isinstance(image, np.ndarray) else image
+            if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] < 3:
+                raise ValueError(f"{who}: image must be uint8 [h, w, 3] in B, G, R order")
+            planes = img.to(base.device)[:, :, :3].permute(2, 0, 1).float().contiguous()
+            colors = resize_nearest(planes, h, w).flip(0).permute(1, 2, 0).to(torch.uint8).contiguous()      # R, G, B
+        kw = dict(colors=colors, fov_deg=fov_deg, inverse=inverse, max_ratio=max_ratio)
+        scene = depth_to_mesh(base.float(), **kw)
+        objects = [depth_to_mesh(blended[k].float(), mask=(masks[k] > 0), **kw) for k in range(blended.shape[0])]
+    return Layers(scene, objects)
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def write_ply(path, mesh_or_points, triangles=None, colors=None):
+    """A binary little-endian PLY from a Mesh, or from points [n, 3] (fp32 -> float, fp64 -> double) with optional triangles [m, 3] and colours uint8
+    [n, 3] (red, green, blue).  Written with numpy on the host: the one place the data leaves the device."""
+    if isinstance(mesh_or_points, Mesh):
+        if triangles is not None or colors is not None:
+            raise ValueError("write_ply: a Mesh carries its own triangles and colors")
+        points, triangles, colors = mesh_or_points.points, mesh_or_points.triangles, mesh_or_points.colors
+    else:
+        points = mesh_or_points
+    pts = _host(points)
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.dtype not in (np.float32, np.float64):
+        raise ValueError(f"write_ply: points must be float32 or float64 [n, 3], got {pts.dtype} {pts.shape}")
+    kind = "float" if pts.dtype == np.float32 else "double"
+    fields = [("x", "<" + pts.dtype.str[1:]), ("y", "<" + pts.dtype.str[1:]), ("z", "<" + pts.dtype.str[1:])]
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {pts.shape[0]}"] + [f"property {kind} {c}" for c in "xyz"]
+    col = None
+    if colors is not None:
+        col = _host(colors)
+        if col.dtype != np.uint8 or col.shape != pts.shape:
+            raise ValueError(f"write_ply: colors must be uint8 {pts.shape}, got {col.dtype} {col.shape}")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        header += [f"property uchar {c}" for c in ("red", "green", "blue")]
+    vert = np.empty(pts.shape[0], dtype=fields)
+    for i, c in enumerate("xyz"):
+        vert[c] = pts[:, i]
+    if col is not None:
+        for i, c in enumerate(("red", "green", "blue")):
+            vert[c] = col[:, i]
+    face = None
+    if triangles is not None:
+        tri = _host(triangles)
+        if tri.ndim != 2 or tri.shape[1] != 3 or tri.dtype.kind not in "iu":
+            raise ValueError(f"write_ply: triangles must be integers [m, 3], got {tri.dtype} {tri.shape}")
+        if tri.size and (tri.min() < 0 or tri.max() >= pts.shape[0]):
+            raise ValueError("write_ply: a triangle indexes a vertex that is not there")
+        face = np.empty(tri.shape[0], dtype=[("n", "u1"), ("v", "<i4", (3,))])
+        face["n"] = 3
+        face["v"] = tri
+        header += [f"element face {tri.shape[0]}", "property list uchar int vertex_indices"]
+    header.append("end_header")
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(vert.tobytes())
+        if face is not None:
+            f.write(face.tobytes())

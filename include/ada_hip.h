@@ -675,6 +675,56 @@ int ada_mask_grid_points_fwd(const int32_t* labels, const int32_t* stats, int32_
                              int32_t small_component_thresh, int32_t grid_step, int32_t* hit, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Depth maps to geometry (reference src/models/amodalsynthdrive/zoedepth/utils/geometry.py, numpy on the host): the unprojection of depth_to_points,
+ * the masked triangle list of create_triangles and a compaction of the vertices a triangle list uses.  Additions under ABI 10.  The launch sequence of
+ * each call depends on the shapes alone (no host read, no flag loop, no cooperative launch, no workgroup waits for another): all three are legal inside
+ * a stream capture.  The library allocates nothing.  Integer outputs are the same bits every run: no atomic decides a position.  h * w < 2^30,
+ * batch <= 65535, h and w down to 1; anything else is ADA_EINVAL.
+ *   The depth value z of a pixel, one rule for all three calls:  inverse == 0: z = (double)depth;  inverse == 1: z = 1 / (a * (double)depth + b), the
+ *   product, the sum and the quotient each rounded once (a, b host doubles).  A vertex is VALID when z is finite and z > 0.
+ *   ada_depth_points_fwd     depth fp32 [batch][h][w] packed.  camera: 21 HOST doubles, read before the call returns: Kinv[9] row-major (the inverse of
+ *     the intrinsics, computed by the caller), R[9] row-major, t[3].  For the pixel in column x, row y, all in fp64, every product and sum rounded once
+ *     and no FMA:
+ *       p_i = ((z Kinv[i,0]) x + (z Kinv[i,1]) y) + (z Kinv[i,2])          q = (-p_0, -p_1, p_2)
+ *       r_i = ((R[i,0] q_0 + R[i,1] q_1) + R[i,2] q_2) + t_i
+ *     With R = I, t = 0 and a Kinv that has a zero in every row (any pinhole camera without skew) this is the reference's float64 result bit for bit;
+ *     for a general pose it differs from numpy's stacked matmul by at most 2 gamma_4 (sum_j |R_ij| |q_j| + |t_i|), gamma_4 = 4u / (1 - 4u), u = 2^-53.
+ *     A vertex whose z is not finite gets NaN in all three coordinates (the reference's inf * 0); a finite z <= 0 is unprojected as computed.
+ *     out_f64  fp64 [batch][h][w][3], out_f32  fp32 [batch][h][w][3] = the fp64 result rounded once to nearest: either may be NULL, not both; 16-byte aligned
+ *     valid    optional uint8 [batch][h][w]: 1 for a valid vertex, else 0
+ *   ada_mesh_triangles_fwd   the candidates are create_triangles's, in its order: cells in raster order, each as (tl, bl, tr) then (br, tr, bl), vertex
+ *     index = y * w + x.  A candidate is kept when each of its three vertices is inside the mask (mask NULL: every vertex is), is valid (depth NULL:
+ *     every vertex is) and, with max_ratio > 0 (needs depth), z_max <= max_ratio * z_min over the three, the product one rounded fp64 multiply.
+ *     mask       optional uint8 [batch][h][w], rows row_pitch_bytes apart (>= w), images image_stride_bytes apart, as ada_mask_label_fwd: a crop is
+ *                read in place; any non-zero byte is inside
+ *     depth      optional fp32 [batch][h][w] packed, with the z rule above
+ *     triangles  int32 [batch][capacity][3]: the first min(count, capacity) kept triangles of each image; rows from count on are untouched
+ *     count      int32 [batch] on the device: the true number, also when it exceeds capacity
+ *     workspace  the caller's, workspace_bytes >= 4 * batch * max(1, ceil((h - 1) (w - 1) / ADA_GEOM_CHUNK)) (checked)
+ *     h == 1 or w == 1: count = 0 (the reference returns an empty list without a mask and raises with one).
+ *     Count, scan, scatter: three launches (csrc/ada_geometry.hip); the predicate is one device function used by the first and the third.
+ *   ada_mesh_compact_fwd     from a triangle list [batch][capacity][3] with its count, and points [batch][h * w][3] of point_bytes 4 (fp32) or 8 (fp64):
+ *     the vertices referenced by at least one of the first min(count, capacity) triangles, numbered 0 .. n - 1 in raster order.
+ *     vertex_count  int32 [batch]: n, also when it exceeds vertex_capacity
+ *     points_out    [batch][vertex_capacity][3], same type as points: vertex k of the new numbering, for k < min(n, vertex_capacity); rows from n on untouched
+ *     colors / colors_out  optional uint8 [batch][h * w][3] -> [batch][vertex_capacity][3], gathered the same way (both or neither)
+ *     triangles     rewritten in place to the new numbering (an index outside 0 .. h * w - 1 is left as it is)
+ *     workspace     the caller's, workspace_bytes >= 4 * batch * (h * w + ceil(h * w / ADA_GEOM_CHUNK)) (checked)
+ *     Clear, mark, count, scan, gather, remap: six launches.
+ * ---------------------------------------------------------------------------------------- */
+#define ADA_GEOM_WAVE 64            /* candidates per ballot */
+#define ADA_GEOM_CHUNK 1024         /* cells / vertices per workgroup of the count and scatter passes */
+#define ADA_GEOM_SCAN_BLOCK 1024    /* workgroup sums per step of the per-image scan */
+int ada_depth_points_fwd(const float* depth, int32_t batch, int32_t h, int32_t w, const double* camera, int32_t inverse, double a, double b,
+                         double* out_f64, float* out_f32, uint8_t* valid, void* stream);
+int ada_mesh_triangles_fwd(const uint8_t* mask, int64_t row_pitch_bytes, int64_t image_stride_bytes, const float* depth, int32_t inverse, double a,
+                           double b, double max_ratio, int32_t batch, int32_t h, int32_t w, int32_t* triangles, int32_t capacity, int32_t* count,
+                           void* workspace, int64_t workspace_bytes, void* stream);
+int ada_mesh_compact_fwd(int32_t* triangles, const int32_t* count, int32_t capacity, int32_t batch, int32_t h, int32_t w, const void* points,
+                         int32_t point_bytes, const uint8_t* colors, void* points_out, uint8_t* colors_out, int32_t vertex_capacity,
+                         int32_t* vertex_count, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Tiled inference for inputs larger than the network's native 518 x 518 (the reference squashes every
  * input to 518 x 518, infer.py:17,84).  ada_tile_blend_fwd merges the per-tile predictions:
  *   tiles     fp32 [B, T, tile_h, tile_w]; tile t covers rows origin_y[t].. and columns origin_x[t].. of the full map
