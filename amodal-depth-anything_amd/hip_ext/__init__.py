@@ -35,6 +35,7 @@ EXPORTS = (
     "ada_mask_label_fwd", "ada_mask_stats_fwd", "ada_mask_keep_area_fwd", "ada_mask_grid_points_fwd",
     "ada_quantile_fwd", "ada_range_map_fwd", "ada_depth_colorize_fwd",
     "ada_depth_points_fwd", "ada_mesh_triangles_fwd", "ada_mesh_compact_fwd",
+    "ada_canny_fwd", "ada_canny_hysteresis_fwd", "ada_edt_fwd", "ada_edge_metric_fwd", "ada_soft_edge_fwd",
     "ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_last_tile",
     "ada_debug_set_timestamps", "ada_debug_set_attention_variant", "ada_debug_count_saturated",
 )
@@ -61,6 +62,12 @@ QUANTILE_WS_BYTES_PER_IMAGE = 33792
 GEOM_WAVE = 64
 GEOM_CHUNK = 1024
 GEOM_SCAN_BLOCK = 1024
+# ada_canny_fwd: pre-transforms and the Gaussian's radius cap; ada_soft_edge_fwd's radius cap; partial rows per image and columns of the edge sums
+CANNY_PRE_NONE, CANNY_PRE_LOG, CANNY_PRE_LOG15 = 0, 1, 2
+CANNY_MAX_RADIUS = 16
+SOFT_EDGE_MAX_RADIUS = 8
+EDGE_SUM_BLOCKS = 256
+EDGE_N_BDE, EDGE_SUM_DT, EDGE_N_GT, EDGE_SUM_DP = range(4)
 
 
 class IgemmArgs(ctypes.Structure):
@@ -222,6 +229,18 @@ def load(path: Optional[str] = None):
     lib.ada_mesh_compact_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                          c_void_p, c_void_p, c_int64, c_void_p]
     lib.ada_mesh_compact_fwd.restype = c_int
+    lib.ada_canny_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]
+    lib.ada_canny_fwd.restype = c_int
+    lib.ada_canny_hysteresis_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.ada_canny_hysteresis_fwd.restype = c_int
+    lib.ada_edt_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.ada_edt_fwd.restype = c_int
+    lib.ada_edge_metric_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_double, c_void_p, c_void_p, c_int64,
+                                        c_void_p]
+    lib.ada_edge_metric_fwd.restype = c_int
+    lib.ada_soft_edge_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.ada_soft_edge_fwd.restype = c_int
     for name in ("ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_set_attention_variant"):
         getattr(lib, name).argtypes = [c_int]
         getattr(lib, name).restype = None
@@ -956,6 +975,98 @@ def depth_colorize(value, lut, out, range64=None, vmin=0.0, vmax=1.0, invalid_ma
     r, g, b, a = (int(c) & 0xff for c in background)
     _check(load().ada_depth_colorize_fwd(pv, B, h, w, pr, float(vmin), float(vmax), pl, pm, float(invalid_val), r | (g << 8) | (b << 16) | (a << 24), po,
                                          _stream()), "ada_depth_colorize_fwd")
+
+
+def canny_hysteresis_workspace_bytes(batch: int, h: int, w: int) -> int:
+    """Bytes of workspace ada_canny_hysteresis_fwd asks for (include/ada_hip.h)."""
+    hw = h * w
+    return 4 * batch * hw + 4 * batch + mask_label_workspace_bytes(batch, h, w) + batch * ((hw // 2 + 2 + 3) // 4 * 4) + (batch * hw + 3) // 4 * 4
+
+
+def edt_workspace_bytes(batch: int, h: int, w: int) -> int:
+    """Bytes of workspace ada_edt_fwd asks for: one int32 per pixel."""
+    return 4 * batch * h * w
+
+
+def edge_sums_workspace_bytes(batch: int, columns: int = 4) -> int:
+    """Bytes of workspace ada_edge_metric_fwd (4 columns) / ada_soft_edge_fwd (2 columns) ask for."""
+    return 8 * batch * EDGE_SUM_BLOCKS * columns
+
+
+def _maps3(who, first, name="image", dtype=torch.float32):
+    if not isinstance(first, torch.Tensor) or first.dim() != 3 or not first.is_contiguous() or first.numel() == 0:
+        raise HipExtError(f"{who}: {name} must be a non-empty contiguous [B, h, w] tensor, got {tuple(getattr(first, 'shape', ()))}")
+    _dev(first, name, dtype)
+    return tuple(first.shape)
+
+
+def _like(who, name, t, ref, dtype, optional=False):
+    if t is None and optional:
+        return None
+    p = _sized(who, name, t, tuple(ref.shape), dtype)
+    if t.device != ref.device:
+        raise HipExtError(f"{who}: {name} on {t.device}, expected {ref.device}")
+    return p
+
+
+def canny_front(image, weights, low_threshold, low_masked, pre=CANNY_PRE_NONE, pre_out=None, smoothed=None, isobel=None, jsobel=None, magnitude=None):
+    """image fp32 [B, h, w] -> low_masked fp32 [B, h, w]: skimage's Canny detector up to the suppressed magnitude (ada_canny_fwd).  ``weights``: device
+    fp64 [2 r + 1], the Gaussian's taps; ``pre``: CANNY_PRE_*; the other maps are optional fp32 stage outputs of image's shape."""
+    who = "canny_front"
+    B, h, w = _maps3(who, image)
+    if not isinstance(weights, torch.Tensor) or weights.dim() != 1 or weights.numel() % 2 != 1 or not weights.is_contiguous() or weights.device != image.device:
+        raise HipExtError(f"{who}: weights must be a contiguous fp64 [2 r + 1] tensor on {image.device}, got {tuple(getattr(weights, 'shape', ()))}")
+    pw = _dev(weights, "weights", torch.float64)
+    outs = [_like(who, n, t, image, torch.float32, optional=n != "low_masked") for n, t in
+            (("low_masked", low_masked), ("pre_out", pre_out), ("smoothed", smoothed), ("isobel", isobel), ("jsobel", jsobel), ("magnitude", magnitude))]
+    _check(load().ada_canny_fwd(image.data_ptr(), B, h, w, int(pre), pw, weights.numel() // 2, float(low_threshold), *outs, _stream()), "ada_canny_fwd")
+
+
+def canny_hysteresis(low_masked, high_threshold, edges, workspace=None):
+    """low_masked fp32 [B, h, w] -> edges uint8 0 / 1 [B, h, w]: the 8-connected components of low_masked > 0 that reach ``high_threshold``
+    (ada_canny_hysteresis_fwd).  ``workspace``: at least canny_hysteresis_workspace_bytes(B, h, w) bytes, allocated when None."""
+    who = "canny_hysteresis"
+    B, h, w = _maps3(who, low_masked, "low_masked")
+    pe = _like(who, "edges", edges, low_masked, torch.uint8)
+    ws, ws_bytes = _bytes_of(who, workspace, canny_hysteresis_workspace_bytes(B, h, w), low_masked.device)
+    _check(load().ada_canny_hysteresis_fwd(low_masked.data_ptr(), B, h, w, float(high_threshold), pe, ws.data_ptr(), ws_bytes, _stream()),
+           "ada_canny_hysteresis_fwd")
+
+
+def edt(edges, out, workspace=None):
+    """edges uint8 [B, h, w] -> out fp64 [B, h, w]: the exact Euclidean distance to the nearest non-zero pixel, +inf where the image has none
+    (ada_edt_fwd).  ``workspace``: at least edt_workspace_bytes(B, h, w) bytes, allocated when None."""
+    who = "edt"
+    B, h, w = _maps3(who, edges, "edges", torch.uint8)
+    po = _like(who, "out", out, edges, torch.float64)
+    ws, ws_bytes = _bytes_of(who, workspace, edt_workspace_bytes(B, h, w), edges.device)
+    _check(load().ada_edt_fwd(edges.data_ptr(), B, h, w, po, ws.data_ptr(), ws_bytes, _stream()), "ada_edt_fwd")
+
+
+def edge_metric_sums(pred_edges, gt_edges, valid, d_target, d_pred, th_acc, sums, workspace=None):
+    """sums fp64 [B, 4] (EDGE_*): count and sum of d_target over pred_edges & valid & (d_target < th_acc), count and sum of d_pred over gt_edges & valid
+    (ada_edge_metric_fwd).  Edge maps and ``valid`` (or None) uint8 [B, h, w], distance maps fp64 [B, h, w]."""
+    who = "edge_metric_sums"
+    B, h, w = _maps3(who, pred_edges, "pred_edges", torch.uint8)
+    pg = _like(who, "gt_edges", gt_edges, pred_edges, torch.uint8)
+    pv = _like(who, "valid", valid, pred_edges, torch.uint8, optional=True)
+    pt, pp = _like(who, "d_target", d_target, pred_edges, torch.float64), _like(who, "d_pred", d_pred, pred_edges, torch.float64)
+    ps = _sized(who, "sums", sums, (B, 4), torch.float64)
+    ws, ws_bytes = _bytes_of(who, workspace, edge_sums_workspace_bytes(B, 4), pred_edges.device)
+    _check(load().ada_edge_metric_fwd(pred_edges.data_ptr(), pg, pv, pt, pp, B, h, w, float(th_acc), ps, ws.data_ptr(), ws_bytes, _stream()),
+           "ada_edge_metric_fwd")
+
+
+def soft_edge(pred, gt, valid, radius, sums, workspace=None):
+    """sums fp64 [B, 2]: the number of valid pixels and the sum over them of min over the (2 radius + 1)^2 shifts of |shift(gt) - pred| (ada_soft_edge_fwd).
+    pred, gt fp32 [B, h, w]; ``valid`` uint8 [B, h, w] or None."""
+    who = "soft_edge"
+    B, h, w = _maps3(who, pred, "pred")
+    pg = _like(who, "gt", gt, pred, torch.float32)
+    pv = _like(who, "valid", valid, pred, torch.uint8, optional=True)
+    ps = _sized(who, "sums", sums, (B, 2), torch.float64)
+    ws, ws_bytes = _bytes_of(who, workspace, edge_sums_workspace_bytes(B, 2), pred.device)
+    _check(load().ada_soft_edge_fwd(pred.data_ptr(), pg, pv, B, h, w, int(radius), ps, ws.data_ptr(), ws_bytes, _stream()), "ada_soft_edge_fwd")
 
 
 # --- tuning / diagnostic hooks (include/ada_hip.h, last section) ---------------------------------

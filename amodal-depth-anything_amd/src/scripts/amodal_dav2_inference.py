@@ -80,19 +80,29 @@ def load_sample(sid: str, occ_image_dir: str, whole_mask_dir: str, observation_d
 
 def run(model: Callable, ids: List[str], occ_image_dir: str, whole_mask_dir: str, observation_depth_dir: str, output_dir: str,
         gt_depth_dir: Optional[str] = None, batch_size: int = 32, device: str = "cuda", evaluate: Optional[Callable] = None,
-        group=None, protocol: str = "legacy", visible_mask_dir: Optional[str] = None, invisible_mask_dir: Optional[str] = None) -> Dict[str, float]:
+        group=None, protocol: str = "legacy", visible_mask_dir: Optional[str] = None, invisible_mask_dir: Optional[str] = None,
+        edge_metrics: bool = False) -> Dict[str, float]:
     """Runs the model over ``ids`` in batches, writes ``{output_dir}/amodal_depth/{id}_depth.png`` (uint16, depth * 65535, :124-125)
     and returns the per-sample metrics averaged over the samples when ground truth is available.  ``evaluate(pred, gt, mask) -> dict``
     (applied to one sample at a time) defaults to the device path.
 
     ``protocol="paper"`` (needs ``gt_depth_dir`` and ``visible_mask_dir``): the evaluation of src/util/validation.py; returns its eight groups
     plus ``"counts"`` (per group and metric, the samples that entered the mean).  ``evaluate`` is then a batch evaluator with the signature of
-    ``validation.evaluate_batch(pred, gt, observation, whole, visible, invisible, valid)``."""
+    ``validation.evaluate_batch(pred, gt, observation, whole, visible, invisible, valid)``.
+
+    ``edge_metrics=True`` (legacy protocol with the default evaluator only) adds ``EdgeAcc``, ``EdgeComp`` and ``soft_edge_error`` per sample
+    (src/util/metric.py), computed on the aligned prediction clamped to [1e-3, 1], materialised in fp32 on the device with torch ops.  The other legacy
+    metrics form the same value inside ada_depth_eval_fwd, where the product and the sum may contract into one FMA: the two maps agree up to one fp32 ulp."""
     if protocol not in ("legacy", "paper"):
         raise ValueError(f"protocol must be 'legacy' or 'paper', got {protocol!r}")
     paper = protocol == "paper"
     if paper and not (gt_depth_dir and visible_mask_dir):
         raise ValueError("protocol='paper' needs gt_depth_dir and visible_mask_dir")
+    if edge_metrics and paper:
+        # the reference's aligned prediction is a float64 array there, and the detector keeps its stages in the image's dtype: only the float32 path exists
+        raise ValueError("edge_metrics is not available with protocol='paper': the edge detector on the device covers float32 maps only")
+    if edge_metrics and (evaluate is not None or not gt_depth_dir):
+        raise ValueError("edge_metrics needs gt_depth_dir and the default evaluator")
     out_depth = os.path.join(output_dir, "amodal_depth")
     os.makedirs(out_depth, exist_ok=True)
     # Metrics follow the reference's evaluation semantics -- one sample at a time (its loader runs batch size 1), then the mean over
@@ -112,7 +122,16 @@ def run(model: Callable, ids: List[str], occ_image_dir: str, whole_mask_dir: str
             import hip_ext as H
             sums = H.depth_eval(pred.contiguous().float(), gt.contiguous().float(), mask.contiguous(), scale_shift=ss.float().contiguous(),
                                 clip=(1e-3, 1.0))                              # aligned prediction clamped to the PNG depth range
-            return [{k: float(v) for k, v in metric._from_sums(sums[b:b + 1]).items()} for b in range(pred.shape[0])]
+            res = [{k: float(v) for k, v in metric._from_sums(sums[b:b + 1]).items()} for b in range(pred.shape[0])]
+            if edge_metrics:
+                pf, gf = pred.contiguous().float(), gt.contiguous().float()
+                ssf = ss.float()
+                aligned = (pf * ssf[:, 0, None, None] + ssf[:, 1, None, None]).clamp(1e-3, 1.0)
+                em = metric.edge_metrics(aligned, gf, mask)
+                for b in range(pred.shape[0]):
+                    res[b]["EdgeAcc"], res[b]["EdgeComp"] = float(em["EdgeAcc"][b]), float(em["EdgeComp"][b])
+                    res[b]["soft_edge_error"] = float(metric.soft_edge_error(aligned[b], gf[b], mask[b]))
+            return res
     elif gt_depth_dir:
         def per_sample(pred, gt, mask):
             return [evaluate(pred[b:b + 1], gt[b:b + 1], mask[b:b + 1]) for b in range(pred.shape[0])]
@@ -186,6 +205,8 @@ def main(argv=None):
                     help="legacy: fit onto the gt inside the whole mask, one mean; paper: the reference's validation protocol (src/util/validation.py)")
     ap.add_argument("--visible_mask_dir", default=None, help="{id}_visible_mask.png (--protocol paper)")
     ap.add_argument("--invisible_mask_dir", default=None, help="{id}_invisible_mask.png; default: whole & ~visible")
+    ap.add_argument("--edge_metrics", action="store_true",
+                    help="also report EdgeAcc, EdgeComp and soft_edge_error per sample (legacy protocol only; needs --gt_depth_dir)")
     ap.add_argument("--output_dir", required=True)
     ap.add_argument("--batch_size", type=int, default=32)
     ap.add_argument("--device", default="cuda")
@@ -212,11 +233,14 @@ def main(argv=None):
         model.load_state_dict(sd, strict=True)
     model = model.eval().to(a.device)
     ids = sample_ids(a.occ_image_dir, a.split_file)
+    if a.edge_metrics and a.protocol == "paper":
+        ap.error("--edge_metrics covers --protocol legacy only: under the paper's protocol the reference's aligned prediction is float64")
     if a.protocol == "paper":
         metrics = run(model, ids, a.occ_image_dir, a.whole_mask_dir, a.observation_depth_dir, a.output_dir, a.gt_depth_dir, a.batch_size, a.device,
                       protocol="paper", visible_mask_dir=a.visible_mask_dir, invisible_mask_dir=a.invisible_mask_dir)
     else:
-        metrics = run(model, ids, a.occ_image_dir, a.whole_mask_dir, a.observation_depth_dir, a.output_dir, a.gt_depth_dir, a.batch_size, a.device)
+        metrics = run(model, ids, a.occ_image_dir, a.whole_mask_dir, a.observation_depth_dir, a.output_dir, a.gt_depth_dir, a.batch_size, a.device,
+                      edge_metrics=a.edge_metrics)
     if metrics and rank == 0:
         with open(os.path.join(a.output_dir, "metrics.json"), "w") as f:
             json.dump(metrics, f, indent=1)

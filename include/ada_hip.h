@@ -725,6 +725,62 @@ int ada_mesh_compact_fwd(int32_t* triangles, const int32_t* count, int32_t capac
                          int32_t* vertex_count, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The edge metrics of the reference's evaluation (reference src/util/metric.py:181-328), which the reference computes on the host with
+ * skimage.feature.canny and scipy.ndimage.distance_transform_edt after copying two full-size maps per sample.  Additions under ABI 10.  All maps are
+ * packed [batch][h][w]; h * w < 2^31, batch <= 65535, h and w down to 1.  No atomics of their own (ada_canny_hysteresis_fwd runs ada_mask_label_fwd, whose
+ * integer atomic-min union-find gives exact, reproducible labels), no host read, nothing allocated: every launch sequence depends on the shapes alone.  The arithmetic contract -- what is rounded where -- is DESIGN.md's "Edge metrics" section; csrc/ada_edges.hip is built without
+ * floating-point contraction.
+ *   ada_canny_fwd            replaces canny(depth, sigma=sigma, mask=None) of extract_edges (metric.py:215) up to the suppressed magnitude, on a FLOAT32
+ *     image with mode 'constant', together with the pre-processing of metric.py:198-210:
+ *     pre        0 identity; 1 to_log (metric.py:169-173): (d > 0) * log(max(d, eps32)); 2 extract_edges' default branch (metric.py:206-210):
+ *                log((d > 0) * max(d, eps32)) / log(1.5), an fp32 division, -inf where d <= 0.  The logarithm is evaluated in fp64 and rounded once.
+ *     weights    DEVICE fp64 [2 radius + 1], computed by the host as scipy's _gaussian_kernel1d does; radius = int(4 sigma + 0.5) <= ADA_CANNY_MAX_RADIUS
+ *     Stages, each stored in fp32: Gaussian along axis 0 then axis 1 (zero outside the image; fp64 accumulation in scipy's symmetric order: centre tap,
+ *     then (in[i - k] + in[i + k]) * w[k] from k = radius down to 1); division by (the same two passes over a map of ones, computed from the
+ *     coordinates) + eps32; ndi.sobel along each axis with mode 'reflect' ([-1, 0, 1] along the axis, [1, 2, 1] along the other, fp64 accumulation);
+ *     magnitude = sqrt(isobel * isobel + jsobel * jsobel) in three fp32 operations; skimage's bilinear non-maximum suppression: off the one-pixel
+ *     border ring, magnitude >= low_threshold, weight and interpolation in fp64, kept when both interpolated neighbours are <= the magnitude.
+ *     low_masked fp32: the kept magnitudes, 0 elsewhere.  pre_out / smoothed / isobel / jsobel / magnitude: optional fp32 stage maps (NULL: not written).
+ *     One workgroup per 32 x 32 tile, halo radius + 2 in LDS: the image is read once.
+ *   ada_canny_hysteresis_fwd replaces canny's double thresholding (ndi.label(low_mask, ones((3, 3))) and good_label[labels]): edges uint8 0 / 1 =
+ *     pixels of the 8-connected components of low_masked > 0 that hold a pixel with low_masked >= high_threshold.  Labels come from
+ *     ada_mask_label_fwd; a per-label byte is set by plain stores of one value, then gathered.
+ *     workspace  workspace_bytes >= 4 batch h w + 4 batch + [ada_mask_label_fwd's] + batch * ceil4(h w / 2 + 2) + ceil4(batch h w)  (checked)
+ *   ada_edt_fwd              replaces ndimage.distance_transform_edt(np.logical_not(edges)) (metric.py:242, 245): out fp64 = the Euclidean distance
+ *     to the nearest non-zero pixel of edges (uint8), 0 on them.  Squared distances are exact integers (h, w <= 32767, else ADA_EUNSUPPORTED): a column
+ *     pass (two scans), a row pass min over x' of (x - x')^2 + g(x')^2 with the row staged through LDS in chunks, one fp64 square root.  An image
+ *     WITHOUT any edge pixel gives +inf everywhere; scipy's output for that input is an artefact of its implementation, not a documented value.
+ *     workspace  workspace_bytes >= 4 batch h w  (checked)
+ *   ada_edge_metric_fwd      the sums behind EdgeAcc / EdgeComp (metric.py:247-256): sums fp64 [batch][4] =
+ *     ADA_EDGE_N_BDE, ADA_EDGE_SUM_DT  count and sum of d_target over pred_edges && valid && d_target < th_acc
+ *     ADA_EDGE_N_GT,  ADA_EDGE_SUM_DP  count and sum of d_pred over gt_edges && valid
+ *     valid      optional uint8 (NULL: every pixel).  workspace_bytes >= 8 * batch * ADA_EDGE_SUM_BLOCKS * 4  (checked)
+ *   ada_soft_edge_fwd        the sums behind soft_edge_error (metric.py:317-328): sums fp64 [batch][2] = the number of valid pixels and the sum over
+ *     them of min over the (2 radius + 1)^2 shifts of |shift(gt) - pred|, the shifted map 0 where it came from outside (shift_2d_replace with
+ *     constant 0); difference and absolute value in fp32.  0 <= radius <= ADA_SOFT_EDGE_MAX_RADIUS.
+ *     workspace_bytes >= 8 * batch * ADA_EDGE_SUM_BLOCKS * 2  (checked)
+ *   Both reductions run in a fixed order (per-thread strided sums, a shuffle tree, ADA_EDGE_SUM_BLOCKS partial rows per image, one tree): the same bits
+ *   every run.
+ * ---------------------------------------------------------------------------------------- */
+#define ADA_CANNY_MAX_RADIUS 16       /* sigma <= 4 */
+#define ADA_SOFT_EDGE_MAX_RADIUS 8
+#define ADA_EDGE_SUM_BLOCKS 256       /* partial rows per image of the two reductions */
+#define ADA_EDGE_N_BDE 0
+#define ADA_EDGE_SUM_DT 1
+#define ADA_EDGE_N_GT 2
+#define ADA_EDGE_SUM_DP 3
+int ada_canny_fwd(const float* image, int32_t batch, int32_t h, int32_t w, int32_t pre, const double* weights, int32_t radius,
+                  float low_threshold, float* low_masked, float* pre_out, float* smoothed, float* isobel, float* jsobel, float* magnitude,
+                  void* stream);
+int ada_canny_hysteresis_fwd(const float* low_masked, int32_t batch, int32_t h, int32_t w, float high_threshold, uint8_t* edges, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+int ada_edt_fwd(const uint8_t* edges, int32_t batch, int32_t h, int32_t w, double* out, void* workspace, int64_t workspace_bytes, void* stream);
+int ada_edge_metric_fwd(const uint8_t* pred_edges, const uint8_t* gt_edges, const uint8_t* valid, const double* d_target, const double* d_pred,
+                        int32_t batch, int32_t h, int32_t w, double th_acc, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
+int ada_soft_edge_fwd(const float* pred, const float* gt, const uint8_t* valid, int32_t batch, int32_t h, int32_t w, int32_t radius, double* sums,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Tiled inference for inputs larger than the network's native 518 x 518 (the reference squashes every
  * input to 518 x 518, infer.py:17,84).  ada_tile_blend_fwd merges the per-tile predictions:
  *   tiles     fp32 [B, T, tile_h, tile_w]; tile t covers rows origin_y[t].. and columns origin_x[t].. of the full map
