@@ -35,6 +35,7 @@ EXPORTS = (
     "ada_mask_label_fwd", "ada_mask_stats_fwd", "ada_mask_keep_area_fwd", "ada_mask_grid_points_fwd",
     "ada_quantile_fwd", "ada_range_map_fwd", "ada_depth_colorize_fwd",
     "ada_depth_points_fwd", "ada_mesh_triangles_fwd", "ada_mesh_compact_fwd",
+    "ada_mesh_project_fwd", "ada_mesh_raster_fwd",
     "ada_canny_fwd", "ada_canny_hysteresis_fwd", "ada_edt_fwd", "ada_edge_metric_fwd", "ada_soft_edge_fwd",
     "ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_last_tile",
     "ada_debug_set_timestamps", "ada_debug_set_attention_variant", "ada_debug_count_saturated",
@@ -62,6 +63,14 @@ QUANTILE_WS_BYTES_PER_IMAGE = 33792
 GEOM_WAVE = 64
 GEOM_CHUNK = 1024
 GEOM_SCAN_BLOCK = 1024
+# ada_mesh_raster_fwd: samples in a box walked by the triangle's own thread / by one wave, a workgroup's tile of a larger box, the walking launch's
+# grid and the least number of its workgroups that share a larger box, the depth modes
+RASTER_SMALL_MAX = 16
+RASTER_WAVE_MAX = 4096
+RASTER_TILE_W, RASTER_TILE_H = 32, 8
+RASTER_WALK_BLOCKS = 2048
+RASTER_WALK_SHARE = 16
+RASTER_OUT_W, RASTER_OUT_Z, RASTER_OUT_NORMALISED = 0, 1, 2
 # ada_canny_fwd: pre-transforms and the Gaussian's radius cap; ada_soft_edge_fwd's radius cap; partial rows per image and columns of the edge sums
 CANNY_PRE_NONE, CANNY_PRE_LOG, CANNY_PRE_LOG15 = 0, 1, 2
 CANNY_MAX_RADIUS = 16
@@ -229,6 +238,11 @@ def load(path: Optional[str] = None):
     lib.ada_mesh_compact_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
                                          c_void_p, c_void_p, c_int64, c_void_p]
     lib.ada_mesh_compact_fwd.restype = c_int
+    lib.ada_mesh_project_fwd.argtypes = [c_void_p, c_int32, c_int32, ctypes.POINTER(c_double), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.ada_mesh_project_fwd.restype = c_int
+    lib.ada_mesh_raster_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_double,
+                                        c_float, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
+    lib.ada_mesh_raster_fwd.restype = c_int
     lib.ada_canny_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p]
     lib.ada_canny_fwd.restype = c_int
@@ -938,6 +952,60 @@ def mesh_compact(triangles, count, h, w, points, points_out, vertex_count, color
     ws, ws_bytes = _bytes_of(who, workspace, mesh_compact_workspace_bytes(B, h, w), triangles.device)
     _check(load().ada_mesh_compact_fwd(pt, pc, cap, B, h, w, pp, points.element_size(), pci, po, pco, vcap, pv, ws.data_ptr(), ws_bytes, _stream()),
            "ada_mesh_compact_fwd")
+
+
+def mesh_raster_workspace_bytes(h: int, w: int, n_triangles: int) -> int:
+    """Bytes of workspace ada_mesh_raster_fwd asks for (include/ada_hip.h)."""
+    return 8 * (h * w + (h * w) % 2) + 16 + 4 * n_triangles
+
+
+def mesh_project(points, camera, x, y, w, pose=False):
+    """The rasteriser's vertex stage (ada_mesh_project_fwd): points [V, 3] fp32 or fp64 -> x, y int32 [V] (snapped to 1/256 pixel) and w fp64 [V] = 1 / z,
+    0 for an invalid vertex.  ``camera``: 16 host doubles fx, fy, cx, cy, R row-major, t; R and t are applied only with ``pose``."""
+    who = "mesh_project"
+    if not isinstance(points, torch.Tensor) or points.dtype not in (torch.float32, torch.float64) or points.dim() != 2 or points.shape[1] != 3:
+        raise HipExtError(f"{who}: points must be an fp32 or fp64 [V, 3] tensor")
+    V = points.shape[0]
+    pp = _sized(who, "points", points, (V, 3), points.dtype)
+    cam = [float(v) for v in camera]
+    if len(cam) != 16:
+        raise HipExtError(f"{who}: camera must hold 16 doubles (fx, fy, cx, cy, R, t), got {len(cam)}")
+    px, py, pw = _sized(who, "x", x, (V,), torch.int32), _sized(who, "y", y, (V,), torch.int32), _sized(who, "w", w, (V,), torch.float64)
+    for name, t in (("x", x), ("y", y), ("w", w)):
+        if t.device != points.device:
+            raise HipExtError(f"{who}: {name} on {t.device}, points on {points.device}")
+    _check(load().ada_mesh_project_fwd(pp, points.element_size(), V, (c_double * 16)(*cam), 1 if pose else 0, px, py, pw, _stream()), "ada_mesh_project_fwd")
+
+
+def mesh_raster(x, y, w, triangles, h, width, depth, index, colors=None, color=None, mode=RASTER_OUT_Z, inverse=None, fill=0.0, fill_color=(128, 128, 128),
+                workspace=None):
+    """Clear, rasterise and resolve (ada_mesh_raster_fwd): vertex records x, y int32 [V], w fp64 [V] and triangles int32 [T, 3] -> depth fp32 [h, width],
+    index int32 [h, width] and, with colors uint8 [V, 3], color uint8 [h, width, 3].  ``mode``: RASTER_OUT_W / _Z / _NORMALISED, the last with
+    ``inverse`` = (a, b).  ``workspace``: at least mesh_raster_workspace_bytes(h, width, T) bytes, 16-byte aligned, allocated when None."""
+    who = "mesh_raster"
+    if not isinstance(triangles, torch.Tensor) or triangles.dim() != 2 or triangles.shape[1] != 3:
+        raise HipExtError(f"{who}: triangles must be an int32 [T, 3] tensor, got {tuple(getattr(triangles, 'shape', ()))}")
+    T = triangles.shape[0]
+    pt = _sized(who, "triangles", triangles, (T, 3), torch.int32)
+    if not isinstance(x, torch.Tensor) or x.dim() != 1:
+        raise HipExtError(f"{who}: x must be an int32 [V] tensor")
+    V = x.shape[0]
+    px, py, pw = _sized(who, "x", x, (V,), torch.int32), _sized(who, "y", y, (V,), torch.int32), _sized(who, "w", w, (V,), torch.float64)
+    pd, pi = _sized(who, "depth", depth, (h, width), torch.float32), _sized(who, "index", index, (h, width), torch.int32)
+    if color is not None and colors is None:
+        raise HipExtError(f"{who}: a color output needs the vertex colors")
+    pci = None if colors is None else _sized(who, "colors", colors, (V, 3), torch.uint8)
+    pco = None if color is None else _sized(who, "color", color, (h, width, 3), torch.uint8)
+    for name, t in (("y", y), ("w", w), ("triangles", triangles), ("index", index), ("colors", colors), ("color", color), ("x", x)):
+        if t is not None and t.device != depth.device:
+            raise HipExtError(f"{who}: {name} on {t.device}, depth on {depth.device}")
+    a, b = (1.0, 0.0) if inverse is None else (float(inverse[0]), float(inverse[1]))
+    rgb = [int(c) for c in fill_color]
+    if len(rgb) != 3 or min(rgb) < 0 or max(rgb) > 255:
+        raise HipExtError(f"{who}: fill_color must hold three values in 0 .. 255, got {fill_color!r}")
+    ws, ws_bytes = _bytes_of(who, workspace, mesh_raster_workspace_bytes(h, width, T), depth.device)
+    _check(load().ada_mesh_raster_fwd(px, py, pw, pci, V, pt, T, h, width, int(mode), a, b, float(fill), rgb[0] | rgb[1] << 8 | rgb[2] << 16, pd, pi, pco,
+                                      ws.data_ptr(), ws_bytes, _stream()), "ada_mesh_raster_fwd")
 
 
 def range_map(depth, range32, out, scale=1.0, shift=0.0, clip=None):

@@ -1,6 +1,10 @@
 """Depth maps to geometry on the device: what the reference does on the host in numpy (src/models/amodalsynthdrive/zoedepth/utils/geometry.py:
 get_intrinsics, depth_to_points, create_triangles) with the maps left in HBM (csrc/ada_geometry.hip), up to the layered meshes of an amodal result.
 
+Meshes are also looked at here: render_mesh / render_meshes / render_layers rasterise them from a camera into a depth map, a colour image and a
+map of the triangle and the mesh each pixel shows (csrc/ada_raster.hip).  The reference hands its meshes to a third-party renderer, so that arithmetic is
+this library's own: include/ada_hip.h states it and tests/_raster_ref.py restates it in numpy.
+
 Exact against the reference: the points of the default pose (R = None, t = None) for any pinhole K without skew, bit for bit in float64, and the
 triangle list, order included (int32 here, int64 there).  A general pose differs from numpy's stacked matmul in the last ulps, within
 2 gamma_4 (sum_j |R_ij| |q_j| + |t_i|) (include/ada_hip.h).  This library's own: the inverse-depth mode z = 1 / (a depth + b), vertex validity
@@ -17,7 +21,8 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import HipExtError, depth_points, mesh_compact, mesh_triangles
+from . import (HipExtError, RASTER_OUT_NORMALISED, RASTER_OUT_W, RASTER_OUT_Z, depth_points, mesh_compact, mesh_project, mesh_raster,
+               mesh_raster_workspace_bytes, mesh_triangles)
 from .image import _as_int
 
 Mesh = namedtuple("Mesh", "points triangles vertex_count triangle_count colors")
@@ -26,6 +31,10 @@ Python ints, colors uint8 [vertex_count, 3] (R, G, B) or None."""
 
 Layers = namedtuple("Layers", "scene objects")
 Layers.__doc__ = """amodal_layers: the scene Mesh (the base depth over every pixel) and a list of K object Meshes (each blended map over its amodal mask)."""
+
+View = namedtuple("View", "depth index owner color")
+View.__doc__ = """A rendered view on the device: depth fp32 [h, w], index int32 [h, w] (the triangle each pixel shows, -1 for background), owner int32 [h, w]
+(the position of that triangle's mesh among the rendered ones, -1 for background), color uint8 [h, w, 3] (R, G, B) or None."""
 
 MAX_PIXELS = 2 ** 30
 
@@ -312,6 +321,188 @@ def amodal_layers(result, image=None, near=1.0, far=10.0, fov_deg=55.0, max_rati
         scene = depth_to_mesh(base.float(), **kw)
         objects = [depth_to_mesh(blended[k].float(), mask=(masks[k] > 0), **kw) for k in range(blended.shape[0])]
     return Layers(scene, objects)
+
+
+_OUT_MODES = {"w": RASTER_OUT_W, "z": RASTER_OUT_Z, "normalised": RASTER_OUT_NORMALISED}
+_OUT_FILL = {"w": 0.0, "z": float("inf"), "normalised": 0.0}      # background: infinitely far
+
+
+def look_at_pose(yaw_deg=0.0, pitch_deg=0.0, shift=(0.0, 0.0, 0.0), pivot_z=None):
+    """(R, t), float64 numpy, of a camera that orbits about the point c = (0, 0, pivot_z) on the optical axis, for render_mesh's ``R``, ``t`` (the
+    reference's "to the target viewpoint" convention, q = R p + t).  Points are in the reference's convention (what depth_to_points returns): x to the
+    left, y up, z forward.  R = Rx(pitch) Ry(yaw), right-handed rotations about +x and +y; t = c - R c + shift, so with a zero ``shift`` the pivot
+    stays where it is and otherwise moves by ``shift``.  ``pivot_z=None`` turns the camera about its own centre."""
+    yaw, pitch = np.deg2rad(np.float64(yaw_deg)), np.deg2rad(np.float64(pitch_deg))
+    cy, sy, cp, sp = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch)
+    Ry = np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]], dtype=np.float64)
+    Rx = np.array([[1.0, 0.0, 0.0], [0.0, cp, -sp], [0.0, sp, cp]], dtype=np.float64)
+    R = Rx @ Ry
+    shift = np.asarray(shift, dtype=np.float64).reshape(-1)
+    if shift.shape != (3,):
+        raise ValueError(f"look_at_pose: shift must hold 3 values, got {shift.shape}")
+    c = np.array([0.0, 0.0, 0.0 if pivot_z is None else float(pivot_z)], dtype=np.float64)
+    return R, c - R @ c + shift
+
+
+def _view_camera(who, h, w, K, fov_deg, R, t):
+    """16 host doubles fx, fy, cx, cy, R, t and whether a pose is applied."""
+    K = get_intrinsics(h, w, fov_deg) if K is None else np.asarray(K, dtype=np.float64)
+    if K.shape != (3, 3):
+        raise ValueError(f"{who}: K must be 3 x 3, got {K.shape}")
+    if not np.all(np.isfinite(K)) or K[0, 1] != 0 or K[1, 0] != 0 or K[2, 0] != 0 or K[2, 1] != 0 or K[2, 2] != 1:
+        raise ValueError(f"{who}: K must be a finite pinhole matrix without skew, [[fx, 0, cx], [0, fy, cy], [0, 0, 1]]")
+    pose = R is not None or t is not None
+    R = np.eye(3) if R is None else np.asarray(R, dtype=np.float64)
+    t = np.zeros(3) if t is None else np.asarray(t, dtype=np.float64).reshape(-1)
+    if R.shape != (3, 3) or t.shape != (3,):
+        raise ValueError(f"{who}: R must be 3 x 3 and t must hold 3 values, got {R.shape}, {t.shape}")
+    return [K[0, 0], K[1, 1], K[0, 2], K[1, 2]] + list(R.reshape(-1)) + list(t), pose
+
+
+def _view_out(who, out, inverse, fill):
+    if out not in _OUT_MODES:
+        raise ValueError(f"{who}: out must be 'z', 'w' or 'normalised', got {out!r}")
+    inverse = _inverse(who, inverse)
+    if out == "normalised":
+        if inverse is None:
+            raise ValueError(f"{who}: out='normalised' needs inverse=(a, b)")
+        if not (inverse[0] == inverse[0] and inverse[1] == inverse[1] and inverse[0] != 0.0):
+            raise ValueError(f"{who}: inverse=(a, b) needs a != 0 and no NaN, got {inverse!r}")
+    return _OUT_MODES[out], (inverse if out == "normalised" else None), _OUT_FILL[out] if fill is None else float(fill)
+
+
+def _fill_color(who, fill_color):
+    try:
+        rgb = [int(c) for c in fill_color]
+    except (TypeError, ValueError):
+        rgb = []
+    if len(rgb) != 3 or min(rgb) < 0 or max(rgb) > 255:
+        raise ValueError(f"{who}: fill_color must hold three values in 0 .. 255, got {fill_color!r}")
+    return tuple(rgb)
+
+
+def _check_part(who, points, triangles, colors):
+    """Types and shapes of one mesh's arrays, before any device is looked at."""
+    for name, a, kinds, what in (("points", points, ("float32", "float64"), "float32 or float64"), ("triangles", triangles, ("int32",), "int32"),
+                                 ("colors", colors, ("uint8",), "uint8")):
+        if a is None and name == "colors":
+            continue
+        if not isinstance(a, (np.ndarray, torch.Tensor)):
+            raise TypeError(f"{who}: {name} must be a numpy array or a torch tensor, got {type(a).__name__}")
+        if str(a.dtype).replace("torch.", "") not in kinds or a.ndim != 2 or a.shape[1] != 3:
+            raise ValueError(f"{who}: {name} must be {what} [n, 3], got {a.dtype} {tuple(a.shape)}")
+    if colors is not None and colors.shape[0] != points.shape[0]:
+        raise ValueError(f"{who}: {colors.shape[0]} colors for {points.shape[0]} points")
+    if points.shape[0] >= 2 ** 31 or triangles.shape[0] >= 2 ** 31:
+        raise ValueError(f"{who}: at most 2^31 - 1 points and triangles")
+
+
+def _stage_part(who, a, device):
+    if isinstance(a, np.ndarray):
+        return _from_numpy(a).to(device)
+    if a.device != device:
+        raise HipExtError(f"{who}: a mesh tensor on {a.device}, expected it on the HIP device {device}")
+    return a.contiguous()
+
+
+@torch.no_grad()
+def _render(who, parts, labels, h, w, K, fov_deg, R, t, out, inverse, fill, fill_color, device):
+    """parts: (points, triangles, colors) per mesh; labels: the owner value of each."""
+    h, w = _grid(who, h, w)
+    cam, pose = _view_camera(who, h, w, K, fov_deg, R, t)
+    mode, ab, fill = _view_out(who, out, inverse, fill)
+    rgb = _fill_color(who, fill_color)
+    if not parts:
+        raise ValueError(f"{who}: nothing to render")
+    for p in parts:
+        _check_part(who, *p)
+    if len({str(p[0].dtype).replace("torch.", "") for p in parts}) > 1:
+        raise ValueError(f"{who}: the meshes' points must share one type")
+    with_color = all(p[2] is not None for p in parts)      # colours are rendered when every mesh has them
+    device = _device_of(who, device, *[a for p in parts for a in p])
+    with torch.cuda.device(device):
+        staged = [tuple(None if a is None else _stage_part(who, a, device) for a in p) for p in parts]
+        if len(staged) == 1:
+            points, tri, col = staged[0]
+        else:
+            starts = np.cumsum([0] + [p[0].shape[0] for p in staged])
+            points = torch.cat([p[0] for p in staged])
+            tri = torch.cat([p[1] + int(s) for p, s in zip(staged, starts)])
+            col = torch.cat([p[2] for p in staged]) if with_color else None
+        V, T = points.shape[0], tri.shape[0]
+        x = torch.empty(V, dtype=torch.int32, device=device)
+        y = torch.empty(V, dtype=torch.int32, device=device)
+        wv = torch.empty(V, dtype=torch.float64, device=device)
+        mesh_project(points, cam, x, y, wv, pose=pose)
+        depth = torch.empty(h, w, dtype=torch.float32, device=device)
+        index = torch.empty(h, w, dtype=torch.int32, device=device)
+        color = torch.empty(h, w, 3, dtype=torch.uint8, device=device) if with_color else None
+        ws = torch.empty((mesh_raster_workspace_bytes(h, w, T) + 15) // 16 * 2, dtype=torch.int64, device=device)
+        mesh_raster(x, y, wv, tri, h, w, depth, index, colors=col, color=color, mode=mode, inverse=ab, fill=fill, fill_color=rgb, workspace=ws)
+        owner = torch.full_like(index, -1)      # scalar comparisons only: no host array crosses, so a stream capture may hold the whole call
+        start = 0
+        for p, label in zip(staged, labels):
+            end = start + p[1].shape[0]
+            if end > start:
+                owner = torch.where((index >= start) & (index < end), int(label), owner)
+            start = end
+    return View(depth, index, owner, color)
+
+
+def _mesh_arrays(who, mesh_or_points, triangles, colors):
+    if isinstance(mesh_or_points, Mesh):
+        if triangles is not None or colors is not None:
+            raise ValueError(f"{who}: a Mesh carries its own triangles and colors")
+        return mesh_or_points.points, mesh_or_points.triangles, mesh_or_points.colors
+    if triangles is None:
+        raise ValueError(f"{who}: points need triangles")
+    return mesh_or_points, triangles, colors
+
+
+def render_mesh(mesh_or_points, h, w, triangles=None, colors=None, K=None, fov_deg=55.0, R=None, t=None, out="z", inverse=None, fill=None,
+                fill_color=(128, 128, 128), device=None) -> View:
+    """A Mesh, or points [V, 3] (fp32 / fp64) with triangles int32 [T, 3] and optional colors uint8 [V, 3], seen by a pinhole camera ``K`` (default
+    get_intrinsics(h, w, fov_deg); no skew) on an h x w target whose samples sit at integer pixel coordinates -- the grid depth_to_points unprojects
+    from, so the identity view of a depth_to_mesh result gives the map back.  ``R``, ``t``: the pose "to the target viewpoint", q = R p + t (see
+    look_at_pose); both None: q = p exactly.  A z-buffer with inclusive edges, the nearest surface wins and the lowest triangle index wins a tie
+    (include/ada_hip.h has the arithmetic); no clipping: a triangle with a vertex behind the camera or beyond +-16384 pixels is dropped.
+
+    ``out``: 'z' depth, 'w' = 1 / z, or 'normalised' = (w - b) / a for ``inverse=(a, b)``, the convention of depth_to_points and amodal_layers --
+    that map goes into hip_ext.image.render_depth / colorize unchanged.  Background takes ``fill`` (default: inf for 'z', 0 otherwise) and
+    ``fill_color``.  View.color is None without vertex colours; View.owner is 0 on the mesh.  Nothing is read back."""
+    who = "render_mesh"
+    part = _mesh_arrays(who, mesh_or_points, triangles, colors)
+    return _render(who, [part], [0], h, w, K, fov_deg, R, t, out, inverse, fill, fill_color, device)
+
+
+def render_meshes(meshes, h, w, K=None, fov_deg=55.0, R=None, t=None, out="z", inverse=None, fill=None, fill_color=(128, 128, 128), device=None) -> View:
+    """Several Meshes into one buffer, as render_mesh: View.owner is the position in ``meshes`` of the mesh whose triangle won, View.index counts the
+    triangles through the meshes in order.  Colours are rendered when every mesh has them.  An empty Mesh is legal and owns nothing."""
+    who = "render_meshes"
+    meshes = list(meshes)
+    for m in meshes:
+        if not isinstance(m, Mesh):
+            raise TypeError(f"{who}: a list of Mesh expected, got {type(m).__name__}")
+    return _render(who, [(m.points, m.triangles, m.colors) for m in meshes], range(len(meshes)), h, w, K, fov_deg, R, t, out, inverse, fill, fill_color, device)
+
+
+def render_layers(layers, h, w, objects=None, scene=True, near=1.0, far=10.0, out="normalised", K=None, fov_deg=55.0, R=None, t=None, fill=None,
+                  fill_color=(128, 128, 128), device=None) -> View:
+    """The scene mesh (``scene=True``) and the object meshes ``objects`` (indices into layers.objects; None: all) of an amodal_layers result in one view.
+    View.owner is 0 for the scene and k + 1 for object k, whichever are shown.  ``near`` / ``far`` / ``fov_deg`` are what amodal_layers was called with:
+    the default ``out='normalised'`` maps depth back to the networks' normalised inverse depth with them, and 'z' / 'w' are metric."""
+    who = "render_layers"
+    if not isinstance(layers, Layers):
+        raise TypeError(f"{who}: a Layers expected, got {type(layers).__name__}")
+    if not (near > 0 and far > near):
+        raise ValueError(f"{who}: 0 < near < far expected, got near={near!r} far={far!r}")
+    chosen = list(range(len(layers.objects))) if objects is None else [_as_int(k) for k in objects]
+    if any(k is None or not 0 <= k < len(layers.objects) for k in chosen):
+        raise ValueError(f"{who}: objects must index the {len(layers.objects)} object meshes, got {objects!r}")
+    meshes = ([layers.scene] if scene else []) + [layers.objects[k] for k in chosen]
+    labels = ([0] if scene else []) + [k + 1 for k in chosen]
+    inverse = (1.0 / near - 1.0 / far, 1.0 / far)
+    return _render(who, [(m.points, m.triangles, m.colors) for m in meshes], labels, h, w, K, fov_deg, R, t, out, inverse, fill, fill_color, device)
 
 
 def _host(a):

@@ -725,6 +725,52 @@ int ada_mesh_compact_fwd(int32_t* triangles, const int32_t* count, int32_t capac
                          int32_t* vertex_count, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Meshes seen from a camera: a z-buffer rasteriser for the meshes above (csrc/ada_raster.hip).  The reference hands its meshes to a third-party
+ * renderer, so this arithmetic is the library's own; tests/_raster_ref.py restates it in numpy and the GPU suite compares bit for bit.  Additions under
+ * ABI 10.  Neither call allocates or reads anything back; the launch sequence depends on the shapes alone: legal inside a stream capture.  The file is
+ * built without floating-point contraction; "rounded" below means every product, sum and quotient is an IEEE fp64 operation of its own.
+ *   ada_mesh_project_fwd     the vertex stage.  points [n_vertices][3] of point_bytes 4 (fp32, widened exactly) or 8 (fp64), in the reference's point
+ *     convention (what ada_depth_points_fwd writes).  camera: 16 HOST doubles, read before the call returns: fx, fy, cx, cy, R[9] row-major, t[3].
+ *       pose == 1:  q_i = ((R[i,0] p_x + R[i,1] p_y) + R[i,2] p_z) + t_i        pose == 0:  q = p exactly (R, t ignored)
+ *       u = fx ((-q_x) / q_z) + cx     v = fy ((-q_y) / q_z) + cy               samples sit at integers: pixel (row i, column j) is (u, v) = (j, i)
+ *     A vertex is VALID when q is finite, 2^-64 <= q_z <= 2^64 and |u|, |v| <= 16384 (the guard band).
+ *     x, y   int32 [n_vertices]: rint(256 u), rint(256 v), round half to even; 0 for an invalid vertex
+ *     w      fp64 [n_vertices]: 1 / q_z; 0 for an invalid vertex -- w == 0 IS the validity flag ada_mesh_raster_fwd reads
+ *   ada_mesh_raster_fwd      clear, bin, walk, resolve: four launches.  triangles int32 [n_triangles][3] index the vertex records; a triangle is
+ *     dropped when an index is outside [0, n_vertices), a vertex is invalid, or A = (X1 - X0)(Y2 - Y0) - (X2 - X0)(Y1 - Y0) is 0.  No clipping, no culling.
+ *     At the sample (Sx, Sy) = (256 j, 256 i), in int64 (the guard band keeps every product below 2^47):
+ *       e0 = (X2 - X1)(Sy - Y1) - (Y2 - Y1)(Sx - X1)    e1 = (X0 - X2)(Sy - Y2) - (Y0 - Y2)(Sx - X2)    e2 = A - e0 - e1;   A < 0: all four negated
+ *     covered iff e0, e1, e2 >= 0 (edges inclusive).  w = w0 + ((double(e1) (w1 - w0) + double(e2) (w2 - w0)) / double(A)), rounded.
+ *     The winner of a sample is the covering triangle with the largest float32(w) (round to nearest even), ties to the LOWEST triangle index: one
+ *     64-bit unsigned atomic maximum of bits(float32(w)) << 32 | (0xFFFFFFFF - id).  Independent of arrival order: the same bytes every run.
+ *     index   int32 [height][width]: the winner, -1 where nothing covers the sample
+ *     depth   fp32 [height][width], from the winner's fp64 w rounded once: ADA_RASTER_OUT_W w; ADA_RASTER_OUT_Z 1 / w; ADA_RASTER_OUT_NORMALISED
+ *             (w - b) / a (a != 0), the inverse of the z rule above; `fill` where index is -1
+ *     colors / color  optional uint8 [n_vertices][3] -> [height][width][3], perspective-correct: n_i = double(e_i) w_i, den = (n0 + n1) + n2,
+ *             channel = ((n0 c0 + n1 c1) + n2 c2) / den, out = min(255, floor(channel + 0.5)); fill_rgb (r | g << 8 | b << 16) where index is -1
+ *     Work: a triangle whose screen-clipped box holds <= ADA_RASTER_SMALL_MAX samples is walked by its own thread; one of <= ADA_RASTER_WAVE_MAX by
+ *     one wave in tiles of 8 x 8 samples; a larger one by a team of at least ADA_RASTER_WALK_SHARE of the walking launch's ADA_RASTER_WALK_BLOCKS
+ *     workgroups in tiles of ADA_RASTER_TILE_W x ADA_RASTER_TILE_H; a tile with one edge function negative at its four corners is skipped.  The two
+ *     lists are filled by one ballot per wave and one counter add; their order cannot reach the output.
+ *     workspace  the caller's, 16-byte aligned, workspace_bytes >= 8 * (height * width rounded up to even) + 16 + 4 * n_triangles (checked)
+ *     height * width < 2^30; n_triangles == 0 (and n_vertices == 0) is legal and gives the fills.
+ * ---------------------------------------------------------------------------------------- */
+#define ADA_RASTER_SMALL_MAX 16       /* samples in a box that the triangle's own thread walks */
+#define ADA_RASTER_WAVE_MAX 4096      /* samples in a box that one wave walks */
+#define ADA_RASTER_TILE_W 32          /* a workgroup's tile of a larger box */
+#define ADA_RASTER_TILE_H 8
+#define ADA_RASTER_WALK_BLOCKS 2048   /* workgroups of the walking launch */
+#define ADA_RASTER_WALK_SHARE 16      /* workgroups that share one of the larger boxes, at least */
+#define ADA_RASTER_OUT_W 0
+#define ADA_RASTER_OUT_Z 1
+#define ADA_RASTER_OUT_NORMALISED 2
+int ada_mesh_project_fwd(const void* points, int32_t point_bytes, int32_t n_vertices, const double* camera, int32_t pose, int32_t* x, int32_t* y,
+                         double* w, void* stream);
+int ada_mesh_raster_fwd(const int32_t* x, const int32_t* y, const double* w, const uint8_t* colors, int32_t n_vertices, const int32_t* triangles,
+                        int32_t n_triangles, int32_t height, int32_t width, int32_t mode, double a, double b, float fill, uint32_t fill_rgb,
+                        float* depth, int32_t* index, uint8_t* color, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The edge metrics of the reference's evaluation (reference src/util/metric.py:181-328), which the reference computes on the host with
  * skimage.feature.canny and scipy.ndimage.distance_transform_edt after copying two full-size maps per sample.  Additions under ABI 10.  All maps are
  * packed [batch][h][w]; h * w < 2^31, batch <= 65535, h and w down to 1.  No atomics of their own (ada_canny_hysteresis_fwd runs ada_mask_label_fwd, whose
