@@ -8,294 +8,14 @@ the CPU (the fp32 CPU oracle under /oracle is test infrastructure and is never i
 from __future__ import annotations
 
 import ctypes
-import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint16, c_void_p
+from ctypes import c_double, c_float
 from typing import Optional
 
 import torch
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
-
-# --- constants mirrored from include/ada_hip.h ------------------------------------------------
-ABI_VERSION = 10
-DT_F32, DT_F16, DT_BF16 = 0, 1, 2
-A_PLAIN, A_CONV3 = 0, 1
-MAP_PLAIN, MAP_PAD, MAP_TOKEN, MAP_SHUFFLE = 0, 1, 2, 3
-EP_BIAS, EP_GELU, EP_GAMMA, EP_RESIDUAL, EP_RELU_OP, EP_SWIGLU, EP_TAIL, EP_RELU_F32 = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40, 0x80
-ACT_NONE, ACT_SIGMOID, ACT_RELU = 0, 1, 2
-
-EXPORTS = (
-    "ada_abi_version", "ada_operand_dtype", "ada_last_error", "ada_igemm", "ada_attention_fwd", "ada_attention_ex",
-    "ada_pos_embed_resize", "ada_layernorm_fwd", "ada_layernorm_ex", "ada_patchify", "ada_write_cls", "ada_bilinear_fwd", "ada_selftest",
-    "ada_minmax_fwd", "ada_depth_stats_fwd", "ada_token_diversity_fwd", "ada_ladder_select_fwd", "ada_normalize_fwd", "ada_blend_fwd", "ada_depth_eval_fwd", "ada_protocol_fit_fwd", "ada_protocol_eval_fwd", "ada_tile_blend_fwd", "ada_dpt_tail_fwd", "ada_tapsum_resize_fwd",
-    "ada_image_prep_fwd", "ada_depth_resize_fwd",
-    "ada_photo_prep_fwd", "ada_mask_prep_fwd", "ada_nearest_resize_fwd", "ada_blend_ex", "ada_depth_render_fwd",
-    "ada_pil_resize_u8_fwd", "ada_label_combine_fwd",
-    "ada_mask_label_fwd", "ada_mask_stats_fwd", "ada_mask_keep_area_fwd", "ada_mask_grid_points_fwd",
-    "ada_quantile_fwd", "ada_range_map_fwd", "ada_depth_colorize_fwd",
-    "ada_depth_points_fwd", "ada_mesh_triangles_fwd", "ada_mesh_compact_fwd",
-    "ada_mesh_project_fwd", "ada_mesh_raster_fwd",
-    "ada_canny_fwd", "ada_canny_hysteresis_fwd", "ada_edt_fwd", "ada_edge_metric_fwd", "ada_soft_edge_fwd",
-    "ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_last_tile",
-    "ada_debug_set_timestamps", "ada_debug_set_attention_variant", "ada_debug_count_saturated",
-)
-
-# indices into the per-image sums of ada_depth_eval_fwd (ADA_EVAL_* in include/ada_hip.h)
-EVAL_N, EVAL_SUM_P, EVAL_SUM_G, EVAL_SUM_PP, EVAL_SUM_PG, EVAL_ABS_REL, EVAL_SQ_REL, EVAL_SQ, EVAL_LOG_SQ, EVAL_LOG, \
-    EVAL_LOG10_ABS, EVAL_D1, EVAL_D2, EVAL_D3, EVAL_INV_SQ = range(15)
-EVAL_NSUM = 16
-# ada_protocol_fit_fwd / ada_protocol_eval_fwd: columns of a fit row (ADA_FIT_*), pixels per chunk and fp64 words of workspace per chunk
-FIT_N, FIT_SUM_P, FIT_SUM_O, FIT_SUM_PP, FIT_SUM_PO, FIT_MIN_P, FIT_MAX_P, FIT_N_VISIBLE, FIT_N_WHOLE, FIT_SCALE, FIT_SHIFT = range(11)
-FIT_NCOL = 12
-PROTOCOL_CHUNK = 4096
-PROTOCOL_WS_DOUBLES = 32
-# ada_pil_resize_u8_fwd's filters (Pillow's own numbers) and ada_label_combine_fwd's casts
-PIL_NEAREST, PIL_BICUBIC = 0, 3
-LABEL_WRAP, LABEL_CLIP = 0, 1
-# ada_quantile_fwd: modes, population flags, quantiles per call, elements per workgroup, bytes of workspace per image
-Q_NUMPY, Q_TORCH = 0, 1
-Q_EXCLUDE_VALUE, Q_POSITIVE_ONLY = 0x1, 0x2
-QUANTILE_MAX_Q = 4
-QUANTILE_CHUNK = 4096
-QUANTILE_WS_BYTES_PER_IMAGE = 33792
-# ada_mesh_triangles_fwd / ada_mesh_compact_fwd: candidates per ballot, cells or vertices per workgroup, workgroup sums per step of the scan
-GEOM_WAVE = 64
-GEOM_CHUNK = 1024
-GEOM_SCAN_BLOCK = 1024
-# ada_mesh_raster_fwd: samples in a box walked by the triangle's own thread / by one wave, a workgroup's tile of a larger box, the walking launch's
-# grid and the least number of its workgroups that share a larger box, the depth modes
-RASTER_SMALL_MAX = 16
-RASTER_WAVE_MAX = 4096
-RASTER_TILE_W, RASTER_TILE_H = 32, 8
-RASTER_WALK_BLOCKS = 2048
-RASTER_WALK_SHARE = 16
-RASTER_OUT_W, RASTER_OUT_Z, RASTER_OUT_NORMALISED = 0, 1, 2
-# ada_canny_fwd: pre-transforms and the Gaussian's radius cap; ada_soft_edge_fwd's radius cap; partial rows per image and columns of the edge sums
-CANNY_PRE_NONE, CANNY_PRE_LOG, CANNY_PRE_LOG15 = 0, 1, 2
-CANNY_MAX_RADIUS = 16
-SOFT_EDGE_MAX_RADIUS = 8
-EDGE_SUM_BLOCKS = 256
-EDGE_N_BDE, EDGE_SUM_DT, EDGE_N_GT, EDGE_SUM_DP = range(4)
-
-
-class IgemmArgs(ctypes.Structure):
-    """struct ada_igemm_args (include/ada_hip.h) -- field order and types must match exactly."""
-    _fields_ = [
-        ("M", c_int32), ("N", c_int32), ("K", c_int32), ("a_mode", c_int32),
-        ("A", c_void_p), ("lda", c_int64),
-        ("Ho", c_int32), ("Wo", c_int32), ("Hp", c_int32), ("Wp", c_int32), ("stride", c_int32),
-        ("W", c_void_p), ("bias", c_void_p), ("gamma", c_void_p), ("res", c_void_p), ("ldr", c_int64),
-        ("res_row_mod", c_int32), ("res_row_off", c_int32), ("flags", c_int32),
-        ("out_f32", c_void_p), ("ldo_f32", c_int64), ("map_f32", c_int32),
-        ("out_op", c_void_p), ("ldo_op", c_int64), ("map_op", c_int32),
-        ("map_h", c_int32), ("map_w", c_int32), ("shuffle_s", c_int32), ("shuffle_c", c_int32),
-        ("tail_w", c_void_p), ("tail_b", c_float), ("tail_act", c_int32),
-        ("split_seg", c_int32), ("a_dup_seg", c_int32),
-        ("tap_cols", c_int32), ("tap_mask", c_uint16 * 16), ("a_wrap", c_int32), ("bias_row_mod", c_int32),
-        ("f8_from", c_int32), ("f8_mid", c_int32), ("f8_scales", ctypes.c_uint32),
-    ]
-
-
-class LayerNormArgs(ctypes.Structure):
-    """struct ada_layernorm_args (include/ada_hip.h)."""
-    _fields_ = [
-        ("in_", c_void_p), ("ld_in", c_int64), ("rows_out", c_int32), ("dim", c_int32), ("group_in", c_int32), ("skip", c_int32),
-        ("weight", c_void_p), ("bias", c_void_p), ("eps", c_float),
-        ("out_op", c_void_p), ("ld_op", c_int64), ("map_op", c_int32), ("map_h", c_int32), ("map_w", c_int32), ("relu", c_int32),
-        ("out_f32", c_void_p), ("ld_f32", c_int64), ("split_seg", c_int32),
-        ("weight2", c_void_p), ("bias2", c_void_p), ("out2_op", c_void_p), ("ld2_op", c_int64),
-        ("out2_group", c_int32), ("out2_skip", c_int32), ("split_seg2", c_int32), ("unshuffle_s", c_int32), ("tap_bias", c_void_p), ("identity", c_int32),
-    ]
-
-
-class HipExtError(RuntimeError):
-    pass
-
-
-_lib = None
-_lib_path = None
-
-
-def library_path(bf16: bool = False) -> str:
-    return os.path.join(_CSRC, "libada_hip_bf16.so" if bf16 else "libada_hip.so")
-
-
-def load(path: Optional[str] = None):
-    """Loads (once) and returns the ctypes handle.  Raises HipExtError when the library is absent."""
-    global _lib, _lib_path
-    if _lib is not None and (path is None or path == _lib_path):
-        return _lib
-    path = path or os.environ.get("ADA_HIP_LIB") or library_path()
-    if not os.path.exists(path):
-        raise HipExtError(
-            f"libada_hip.so not found at {path}: build it with `python {os.path.join(_CSRC, 'build.py')}` "
-            "(there is no CPU fallback for the HIP path)")
-    try:
-        lib = ctypes.CDLL(path)
-    except OSError as e:  # pragma: no cover
-        raise HipExtError(f"cannot load {path}: {e}") from e
-    for name in EXPORTS:
-        if not hasattr(lib, name):
-            raise HipExtError(f"{path} does not export {name}")
-    lib.ada_abi_version.restype = c_int
-    lib.ada_operand_dtype.restype = c_int
-    lib.ada_last_error.restype = c_char_p
-    lib.ada_igemm.argtypes = [ctypes.POINTER(IgemmArgs), c_void_p]
-    lib.ada_igemm.restype = c_int
-    lib.ada_pos_embed_resize.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_double, c_void_p, c_void_p]
-    lib.ada_pos_embed_resize.restype = c_int
-    lib.ada_attention_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]
-    lib.ada_attention_fwd.restype = c_int
-    lib.ada_attention_ex.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int32, c_void_p]
-    lib.ada_attention_ex.restype = c_int
-    lib.ada_layernorm_fwd.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_float,
-                                      c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p]
-    lib.ada_layernorm_fwd.restype = c_int
-    lib.ada_layernorm_ex.argtypes = [ctypes.POINTER(LayerNormArgs), c_void_p]
-    lib.ada_layernorm_ex.restype = c_int
-    lib.ada_patchify.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
-                                 ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p, c_int64, c_int32, c_void_p]
-    lib.ada_patchify.restype = c_int
-    lib.ada_write_cls.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
-    lib.ada_write_cls.restype = c_int
-    lib.ada_bilinear_fwd.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64,
-                                     c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p]
-    lib.ada_bilinear_fwd.restype = c_int
-    lib.ada_selftest.argtypes = [c_void_p, c_int64, c_void_p]
-    lib.ada_selftest.restype = c_int
-    lib.ada_minmax_fwd.argtypes = [c_void_p, c_int32, c_int64, c_void_p, c_void_p]
-    lib.ada_minmax_fwd.restype = c_int
-    lib.ada_depth_stats_fwd.argtypes = [c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p]
-    lib.ada_depth_stats_fwd.restype = c_int
-    lib.ada_token_diversity_fwd.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p]
-    lib.ada_token_diversity_fwd.restype = c_int
-    lib.ada_ladder_select_fwd.argtypes = [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_double,
-                                          ctypes.c_double, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.ada_ladder_select_fwd.restype = c_int
-    lib.ada_normalize_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]
-    lib.ada_normalize_fwd.restype = c_int
-    lib.ada_blend_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]
-    lib.ada_blend_fwd.restype = c_int
-    lib.ada_tile_blend_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]
-    lib.ada_tile_blend_fwd.restype = c_int
-    lib.ada_dpt_tail_fwd.argtypes = [c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
-                                     c_float, c_int32, c_void_p, c_void_p]
-    lib.ada_dpt_tail_fwd.restype = c_int
-    lib.ada_tapsum_resize_fwd.argtypes = [c_void_p, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]
-    lib.ada_tapsum_resize_fwd.restype = c_int
-    lib.ada_depth_eval_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_float, c_float, c_void_p, c_void_p]
-    lib.ada_depth_eval_fwd.restype = c_int
-    lib.ada_protocol_fit_fwd.argtypes = [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]
-    lib.ada_protocol_fit_fwd.restype = c_int
-    lib.ada_protocol_eval_fwd.argtypes = [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_int32, c_int32, c_int32, c_void_p, c_void_p,
-                                          c_int64, c_void_p]
-    lib.ada_protocol_eval_fwd.restype = c_int
-    lib.ada_image_prep_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32, c_int32,
-                                       ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p, c_void_p]
-    lib.ada_image_prep_fwd.restype = c_int
-    lib.ada_depth_resize_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]
-    lib.ada_depth_resize_fwd.restype = c_int
-    lib.ada_photo_prep_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
-    lib.ada_photo_prep_fwd.restype = c_int
-    lib.ada_mask_prep_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
-    lib.ada_mask_prep_fwd.restype = c_int
-    lib.ada_nearest_resize_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]
-    lib.ada_nearest_resize_fwd.restype = c_int
-    lib.ada_blend_ex.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]
-    lib.ada_blend_ex.restype = c_int
-    lib.ada_depth_render_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_float, c_float, c_void_p, c_void_p, c_int32, ctypes.c_uint32,
-                                         c_double, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
-    lib.ada_depth_render_fwd.restype = c_int
-    lib.ada_pil_resize_u8_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
-                                          c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.ada_pil_resize_u8_fwd.restype = c_int
-    lib.ada_label_combine_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
-                                          c_void_p, c_void_p]
-    lib.ada_label_combine_fwd.restype = c_int
-    lib.ada_mask_label_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
-    lib.ada_mask_label_fwd.restype = c_int
-    lib.ada_mask_stats_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]
-    lib.ada_mask_stats_fwd.restype = c_int
-    lib.ada_mask_keep_area_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
-    lib.ada_mask_keep_area_fwd.restype = c_int
-    lib.ada_mask_grid_points_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]
-    lib.ada_mask_grid_points_fwd.restype = c_int
-    lib.ada_quantile_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int64, ctypes.POINTER(c_double), c_int32, c_int32, c_int32, c_double, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_int64, c_void_p]
-    lib.ada_quantile_fwd.restype = c_int
-    lib.ada_range_map_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int64, c_float, c_float, c_int32, c_float, c_float, c_void_p, c_void_p]
-    lib.ada_range_map_fwd.restype = c_int
-    lib.ada_depth_colorize_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_double, c_double, c_void_p, c_void_p, c_double, ctypes.c_uint32,
-                                           c_void_p, c_void_p]
-    lib.ada_depth_colorize_fwd.restype = c_int
-    lib.ada_depth_points_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, ctypes.POINTER(c_double), c_int32, c_double, c_double, c_void_p, c_void_p,
-                                         c_void_p, c_void_p]
-    lib.ada_depth_points_fwd.restype = c_int
-    lib.ada_mesh_triangles_fwd.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_double, c_double, c_double, c_int32, c_int32, c_int32, c_void_p,
-                                           c_int32, c_void_p, c_void_p, c_int64, c_void_p]
-    lib.ada_mesh_triangles_fwd.restype = c_int
-    lib.ada_mesh_compact_fwd.argtypes = [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32,
-                                         c_void_p, c_void_p, c_int64, c_void_p]
-    lib.ada_mesh_compact_fwd.restype = c_int
-    lib.ada_mesh_project_fwd.argtypes = [c_void_p, c_int32, c_int32, ctypes.POINTER(c_double), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.ada_mesh_project_fwd.restype = c_int
-    lib.ada_mesh_raster_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_double,
-                                        c_float, ctypes.c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
-    lib.ada_mesh_raster_fwd.restype = c_int
-    lib.ada_canny_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                  c_void_p, c_void_p]
-    lib.ada_canny_fwd.restype = c_int
-    lib.ada_canny_hysteresis_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_int64, c_void_p]
-    lib.ada_canny_hysteresis_fwd.restype = c_int
-    lib.ada_edt_fwd.argtypes = [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]
-    lib.ada_edt_fwd.restype = c_int
-    lib.ada_edge_metric_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_double, c_void_p, c_void_p, c_int64,
-                                        c_void_p]
-    lib.ada_edge_metric_fwd.restype = c_int
-    lib.ada_soft_edge_fwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]
-    lib.ada_soft_edge_fwd.restype = c_int
-    for name in ("ada_debug_set_tile", "ada_debug_set_variant", "ada_debug_set_group", "ada_debug_set_attention_variant"):
-        getattr(lib, name).argtypes = [c_int]
-        getattr(lib, name).restype = None
-    for name in ("ada_debug_set_timestamps",):
-        getattr(lib, name).argtypes = [c_void_p]
-        getattr(lib, name).restype = None
-    lib.ada_debug_count_saturated.argtypes = [c_void_p, c_int64, c_void_p, c_void_p]
-    lib.ada_debug_count_saturated.restype = c_int
-    lib.ada_debug_last_tile.argtypes = []
-    lib.ada_debug_last_tile.restype = c_int
-    if lib.ada_abi_version() != ABI_VERSION:
-        raise HipExtError(f"{path}: ABI version {lib.ada_abi_version()} != binding version {ABI_VERSION}")
-    _lib, _lib_path = lib, path
-    return lib
-
-
-def operand_dtype() -> torch.dtype:
-    """torch dtype of the contraction operands the loaded library was built for."""
-    return torch.float16 if load().ada_operand_dtype() == DT_F16 else torch.bfloat16
-
-
-def _check(rc: int, what: str):
-    if rc != 0:
-        msg = load().ada_last_error().decode(errors="replace")
-        raise HipExtError(f"{what} failed (rc={rc}): {msg}")
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _dev(t: torch.Tensor, name: str, dtype=None) -> int:
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise HipExtError(f"{name}: expected a tensor on a HIP device (the HIP path has no CPU fallback)")
-    if dtype is not None and t.dtype != dtype:
-        raise HipExtError(f"{name}: expected dtype {dtype}, got {t.dtype}")
-    return t.data_ptr()
-
-
-def _opt(t: Optional[torch.Tensor], name: str, dtype=None):
-    return None if t is None else _dev(t, name, dtype)
+from ._abi import *  # noqa: F401,F403 -- _abi.__all__: the constants, EXPORTS / PROTOTYPES, IgemmArgs, LayerNormArgs, HipExtError, library_path, load, operand_dtype
+from ._abi import _check, _stream
+from ._args import _bytes_of, _check_src_extent, _dev, _like, _maps3, _opt, _same_device, _sized, _u8
 
 
 class KernelTimer:
@@ -462,8 +182,9 @@ def tapsum_resize(inp, ld_in, batch, hi, wi, ho, wo, channels, bias, out, ld_out
 def minmax(inp, minmax_out):
     """inp: fp32 [B, ...] contiguous -> minmax_out fp32 [B, 2]."""
     B = inp.shape[0]
-    _check(load().ada_minmax_fwd(_dev(inp, "in", torch.float32), B, inp.numel() // B, _dev(minmax_out, "minmax", torch.float32), _stream()),
-           "ada_minmax_fwd")
+    pi, pm = _dev(inp, "in", torch.float32), _dev(minmax_out, "minmax", torch.float32)
+    _same_device("minmax", "in", inp, minmax=minmax_out)
+    _check(load().ada_minmax_fwd(pi, B, inp.numel() // B, pm, _stream()), "ada_minmax_fwd")
 
 
 def depth_stats(inp, sums, act=ACT_SIGMOID):
@@ -517,14 +238,16 @@ def ladder_select(stat_sums, stat_div, stat_in, thr, thr3, div, div_in, has2, ha
 
 def normalize(inp, minmax_in, norm=None, obs=None):
     B = inp.shape[0]
-    _check(load().ada_normalize_fwd(_dev(inp, "in", torch.float32), _dev(minmax_in, "minmax", torch.float32), B, inp.numel() // B,
-                                    _opt(norm, "norm", torch.float32), _opt(obs, "obs", torch.float32), _stream()), "ada_normalize_fwd")
+    pi, pm, pn, po = _dev(inp, "in", torch.float32), _dev(minmax_in, "minmax", torch.float32), _opt(norm, "norm", torch.float32), _opt(obs, "obs", torch.float32)
+    _same_device("normalize", "in", inp, minmax=minmax_in, norm=norm, obs=obs)
+    _check(load().ada_normalize_fwd(pi, pm, B, inp.numel() // B, pn, po, _stream()), "ada_normalize_fwd")
 
 
 def blend(amodal, base, mask, out):
     B, H, W = amodal.shape[0], amodal.shape[-2], amodal.shape[-1]
-    _check(load().ada_blend_fwd(_dev(amodal, "amodal", torch.float32), _dev(base, "base", torch.float32), _dev(mask, "mask", torch.float32),
-                                B, H, W, _dev(out, "out", torch.float32), _stream()), "ada_blend_fwd")
+    pa, pb, pm, po = _dev(amodal, "amodal", torch.float32), _dev(base, "base", torch.float32), _dev(mask, "mask", torch.float32), _dev(out, "out", torch.float32)
+    _same_device("blend", "amodal", amodal, base=base, mask=mask, out=out)
+    _check(load().ada_blend_fwd(pa, pb, pm, B, H, W, po, _stream()), "ada_blend_fwd")
 
 
 def blend_ex(amodal, base, mask, out, scale_shift=None):
@@ -532,16 +255,18 @@ def blend_ex(amodal, base, mask, out, scale_shift=None):
     B, H, W = amodal.shape[0], amodal.shape[-2], amodal.shape[-1]
     if scale_shift is not None and (tuple(scale_shift.shape) != (B, 2) or not scale_shift.is_contiguous()):
         raise HipExtError(f"blend_ex: scale_shift must be contiguous [{B}, 2], got {tuple(scale_shift.shape)}")
-    _check(load().ada_blend_ex(_dev(amodal, "amodal", torch.float32), _dev(base, "base", torch.float32), _dev(mask, "mask", torch.float32),
-                               _opt(scale_shift, "scale_shift", torch.float32), B, H, W, _dev(out, "out", torch.float32), _stream()), "ada_blend_ex")
+    pa, pb, pm, po = _dev(amodal, "amodal", torch.float32), _dev(base, "base", torch.float32), _dev(mask, "mask", torch.float32), _dev(out, "out", torch.float32)
+    ps = _opt(scale_shift, "scale_shift", torch.float32)
+    _same_device("blend_ex", "amodal", amodal, base=base, mask=mask, scale_shift=scale_shift, out=out)
+    _check(load().ada_blend_ex(pa, pb, pm, ps, B, H, W, po, _stream()), "ada_blend_ex")
 
 
 def tile_blend(tiles, origin_y, origin_x, height, width, ramp, out):
     """tiles fp32 [B, T, th, tw]; origin_y / origin_x int32 [T] on the device; out fp32 [B, height, width] (ada_tile_blend_fwd)."""
     B, T, th, tw = tiles.shape
-    _check(load().ada_tile_blend_fwd(_dev(tiles, "tiles", torch.float32), B, T, th, tw, _dev(origin_y, "origin_y", torch.int32),
-                                     _dev(origin_x, "origin_x", torch.int32), height, width, ramp, _dev(out, "out", torch.float32), _stream()),
-           "ada_tile_blend_fwd")
+    pt, py, px, po = _dev(tiles, "tiles", torch.float32), _dev(origin_y, "origin_y", torch.int32), _dev(origin_x, "origin_x", torch.int32), _dev(out, "out", torch.float32)
+    _same_device("tile_blend", "tiles", tiles, origin_y=origin_y, origin_x=origin_x, out=out)
+    _check(load().ada_tile_blend_fwd(pt, B, T, th, tw, py, px, height, width, ramp, po, _stream()), "ada_tile_blend_fwd")
 
 
 def depth_eval(pred, gt, mask=None, scale_shift=None, clip=None) -> torch.Tensor:
@@ -551,14 +276,14 @@ def depth_eval(pred, gt, mask=None, scale_shift=None, clip=None) -> torch.Tensor
     n = pred[0].numel()
     if gt.shape != pred.shape or (mask is not None and mask.shape != pred.shape):
         raise HipExtError(f"depth_eval: shape mismatch pred {tuple(pred.shape)} gt {tuple(gt.shape)}")
-    if mask is not None and mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
+    if mask is not None and mask.dtype == torch.bool and not mask.is_contiguous():
+        mask = mask.to(torch.uint8)      # a packed copy: the kernel reads B * n consecutive bytes
+    mask = _u8(mask)
+    pp, pg, pm, ps = _dev(pred, "pred", torch.float32), _dev(gt, "gt", torch.float32), _opt(mask, "mask", torch.uint8), _opt(scale_shift, "scale_shift", torch.float32)
+    _same_device("depth_eval", "pred", pred, gt=gt, mask=mask, scale_shift=scale_shift)
     sums = torch.empty(B, EVAL_NSUM, dtype=torch.float64, device=pred.device)
     lo, hi = (float(clip[0]), float(clip[1])) if clip is not None else (0.0, 0.0)
-    _check(load().ada_depth_eval_fwd(_dev(pred, "pred", torch.float32), _dev(gt, "gt", torch.float32),
-                                     _dev(mask, "mask", torch.uint8) if mask is not None else None, B, n,
-                                     _dev(scale_shift, "scale_shift", torch.float32) if scale_shift is not None else None,
-                                     lo, hi, _dev(sums, "sums", torch.float64), _stream()), "ada_depth_eval_fwd")
+    _check(load().ada_depth_eval_fwd(pp, pg, pm, B, n, ps, lo, hi, sums.data_ptr(), _stream()), "ada_depth_eval_fwd")
     return sums
 
 
@@ -570,17 +295,14 @@ def protocol_workspace_bytes(batch: int, h: int, w: int) -> int:
 def _protocol_maps(who, pred, maps):
     """pred fp32 [B, hp, wp]; every (name, tensor, dtype, optional) of ``maps`` [B, h, w] with one (h, w), contiguous, on pred's device (bool masks are
     viewed as uint8).  Returns (B, hp, wp, h, w, device pointers in the order of ``maps``)."""
-    if not isinstance(pred, torch.Tensor) or pred.dim() != 3 or not pred.is_contiguous():
-        raise HipExtError(f"{who}: pred must be a contiguous [B, hp, wp] tensor, got {tuple(getattr(pred, 'shape', ()))}")
-    _dev(pred, "pred", torch.float32)
-    B, hp, wp = pred.shape
+    B, hp, wp = _maps3(who, pred, "pred")
     shape, ptrs = None, []
     for name, t, dtype, optional in maps:
         if t is None and optional:
             ptrs.append(None)
             continue
-        if isinstance(t, torch.Tensor) and t.dtype == torch.bool and dtype == torch.uint8 and t.is_contiguous():
-            t = t.view(torch.uint8)
+        if dtype == torch.uint8:
+            t = _u8(t)
         ptrs.append(_dev(t, name, dtype))
         if t.dim() != 3 or not t.is_contiguous() or t.shape[0] != B or t.device != pred.device:
             raise HipExtError(f"{who}: {name} must be a contiguous [{B}, h, w] tensor on {pred.device}, got {tuple(t.shape)} on {t.device}")
@@ -590,24 +312,15 @@ def _protocol_maps(who, pred, maps):
     return B, hp, wp, shape[1], shape[2], ptrs
 
 
-def _protocol_workspace(who, workspace, need, device):
-    if workspace is None:
-        return torch.empty(need // 8, dtype=torch.float64, device=device)
-    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != device:
-        raise HipExtError(f"{who}: workspace must be a contiguous tensor on {device}")
-    return workspace
-
-
 def protocol_fit(pred, observation, visible, whole, workspace=None) -> torch.Tensor:
     """Fit rows fp64 [B, FIT_NCOL] of the prediction (fp32 [B, hp, wp], gathered to the maps' size by ATen's nearest rule) onto ``observation`` (fp32
     [B, h, w]) over ``visible`` (uint8 / bool [B, h, w]), with the pixel counts of ``visible`` and ``whole`` (ada_protocol_fit_fwd).  ``workspace``:
     any contiguous device tensor of at least protocol_workspace_bytes(B, h, w) bytes, allocated when None."""
     B, hp, wp, h, w, (po, pv, pw) = _protocol_maps("protocol_fit", pred, (("observation", observation, torch.float32, False),
                                                                            ("visible", visible, torch.uint8, False), ("whole", whole, torch.uint8, False)))
-    ws = _protocol_workspace("protocol_fit", workspace, protocol_workspace_bytes(B, h, w), pred.device)
+    ws, ws_bytes = _bytes_of("protocol_fit", workspace, protocol_workspace_bytes(B, h, w), pred.device)
     fit = torch.empty(B, FIT_NCOL, dtype=torch.float64, device=pred.device)
-    _check(load().ada_protocol_fit_fwd(pred.data_ptr(), hp, wp, po, pv, pw, B, h, w, fit.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
-           "ada_protocol_fit_fwd")
+    _check(load().ada_protocol_fit_fwd(pred.data_ptr(), hp, wp, po, pv, pw, B, h, w, fit.data_ptr(), ws.data_ptr(), ws_bytes, _stream()), "ada_protocol_fit_fwd")
     return fit
 
 
@@ -618,10 +331,10 @@ def protocol_eval(pred, gt, region, valid, fit, eps=1e-5, workspace=None) -> tor
                                                                             ("valid", valid, torch.uint8, True)))
     if not isinstance(fit, torch.Tensor) or tuple(fit.shape) != (B, FIT_NCOL) or not fit.is_contiguous() or fit.device != pred.device:
         raise HipExtError(f"protocol_eval: fit must be a contiguous [{B}, {FIT_NCOL}] tensor on {pred.device}, got {tuple(getattr(fit, 'shape', ()))}")
-    ws = _protocol_workspace("protocol_eval", workspace, protocol_workspace_bytes(B, h, w), pred.device)
+    ws, ws_bytes = _bytes_of("protocol_eval", workspace, protocol_workspace_bytes(B, h, w), pred.device)
     sums = torch.empty(B, 2, EVAL_NSUM, dtype=torch.float64, device=pred.device)
     _check(load().ada_protocol_eval_fwd(pred.data_ptr(), hp, wp, pg, pr, pv, _dev(fit, "fit", torch.float64), float(eps), B, h, w, sums.data_ptr(), ws.data_ptr(),
-                                        ws.numel() * ws.element_size(), _stream()), "ada_protocol_eval_fwd")
+                                        ws_bytes, _stream()), "ada_protocol_eval_fwd")
     return sums
 
 
@@ -630,8 +343,9 @@ def image_prep(src, batch, hi, wi, channels, row_pitch, image_stride, ho, wo, me
     out fp32 [batch, 3, ho, wo]: RGB / 255, cv2 INTER_CUBIC resize, (v - mean) / std (ada_image_prep_fwd)."""
     m = (c_float * 3)(*mean)
     sd = (c_float * 3)(*std)
-    _check(load().ada_image_prep_fwd(_dev(src, "src", torch.uint8), batch, hi, wi, channels, row_pitch, image_stride, ho, wo, m, sd,
-                                     _dev(out, "out", torch.float32), _stream()), "ada_image_prep_fwd")
+    ps, po = _dev(src, "src", torch.uint8), _dev(out, "out", torch.float32)
+    _same_device("image_prep", "src", src, out=out)
+    _check(load().ada_image_prep_fwd(ps, batch, hi, wi, channels, row_pitch, image_stride, ho, wo, m, sd, po, _stream()), "ada_image_prep_fwd")
 
 
 def depth_resize(inp, out):
@@ -639,18 +353,9 @@ def depth_resize(inp, out):
     if not (inp.is_contiguous() and out.is_contiguous()) or inp.dim() != 3 or out.dim() != 3 or inp.shape[0] != out.shape[0]:
         raise HipExtError(f"depth_resize: contiguous [B, H, W] tensors required, got {tuple(inp.shape)} -> {tuple(out.shape)}")
     B, hi, wi = inp.shape
-    _check(load().ada_depth_resize_fwd(_dev(inp, "in", torch.float32), B, hi, wi, out.shape[1], out.shape[2], _dev(out, "out", torch.float32), _stream()),
-           "ada_depth_resize_fwd")
-
-
-def _check_src_extent(who, src, need):
-    """``src`` (uint8, possibly a strided view) must have ``need`` bytes from its first element to the end of its storage: the kernels read
-    (hi - 1) * row_pitch + a row's bytes (per image) from that pointer, whatever the view's own shape says."""
-    if not isinstance(src, torch.Tensor) or src.dtype != torch.uint8:
-        return      # _dev reports it
-    have = src.untyped_storage().nbytes() - src.storage_offset()
-    if min(need, have) < 0 or have < need:
-        raise HipExtError(f"{who}: src holds {have} bytes from its first pixel, the given sizes and pitches read {need}")
+    pi, po = _dev(inp, "in", torch.float32), _dev(out, "out", torch.float32)
+    _same_device("depth_resize", "in", inp, out=out)
+    _check(load().ada_depth_resize_fwd(pi, B, hi, wi, out.shape[1], out.shape[2], po, _stream()), "ada_depth_resize_fwd")
 
 
 def photo_prep(src, hi, wi, channels, row_pitch, ho, wo, raw_out=None, near_out=None):
@@ -660,8 +365,9 @@ def photo_prep(src, hi, wi, channels, row_pitch, ho, wo, raw_out=None, near_out=
         if t is not None and (t.numel() != 3 * ho * wo or not t.is_contiguous()):
             raise HipExtError(f"photo_prep: {name} must be contiguous with 3 x {ho} x {wo} elements, got {tuple(t.shape)}")
     _check_src_extent("photo_prep", src, (hi - 1) * row_pitch + wi * channels)
-    _check(load().ada_photo_prep_fwd(_dev(src, "src", torch.uint8), hi, wi, channels, row_pitch, ho, wo, _opt(raw_out, "raw_out", torch.float32),
-                                     _opt(near_out, "near_out", torch.float32), _stream()), "ada_photo_prep_fwd")
+    ps, pr, pn = _dev(src, "src", torch.uint8), _opt(raw_out, "raw_out", torch.float32), _opt(near_out, "near_out", torch.float32)
+    _same_device("photo_prep", "src", src, raw_out=raw_out, near_out=near_out)
+    _check(load().ada_photo_prep_fwd(ps, hi, wi, channels, row_pitch, ho, wo, pr, pn, _stream()), "ada_photo_prep_fwd")
 
 
 def mask_prep(src, batch, hi, wi, row_pitch, image_stride, ho, wo, out01, out_pm1=None):
@@ -671,8 +377,9 @@ def mask_prep(src, batch, hi, wi, row_pitch, image_stride, ho, wo, out01, out_pm
         if t is not None and (t.numel() != batch * ho * wo or not t.is_contiguous()):
             raise HipExtError(f"mask_prep: {name} must be contiguous with {batch} x {ho} x {wo} elements, got {tuple(t.shape)}")
     _check_src_extent("mask_prep", src, (batch - 1) * image_stride + (hi - 1) * row_pitch + wi)
-    _check(load().ada_mask_prep_fwd(_dev(src, "src", torch.uint8), batch, hi, wi, row_pitch, image_stride, ho, wo, _dev(out01, "out01", torch.float32),
-                                    _opt(out_pm1, "out_pm1", torch.float32), _stream()), "ada_mask_prep_fwd")
+    ps, p01, pm1 = _dev(src, "src", torch.uint8), _dev(out01, "out01", torch.float32), _opt(out_pm1, "out_pm1", torch.float32)
+    _same_device("mask_prep", "src", src, out01=out01, out_pm1=out_pm1)
+    _check(load().ada_mask_prep_fwd(ps, batch, hi, wi, row_pitch, image_stride, ho, wo, p01, pm1, _stream()), "ada_mask_prep_fwd")
 
 
 def nearest_resize(inp, out):
@@ -680,8 +387,9 @@ def nearest_resize(inp, out):
     if not (inp.is_contiguous() and out.is_contiguous()) or inp.dim() != 3 or out.dim() != 3 or inp.shape[0] != out.shape[0]:
         raise HipExtError(f"nearest_resize: contiguous [B, H, W] tensors required, got {tuple(inp.shape)} -> {tuple(out.shape)}")
     B, hi, wi = inp.shape
-    _check(load().ada_nearest_resize_fwd(_dev(inp, "in", torch.float32), B, hi, wi, out.shape[1], out.shape[2], _dev(out, "out", torch.float32), _stream()),
-           "ada_nearest_resize_fwd")
+    pi, po = _dev(inp, "in", torch.float32), _dev(out, "out", torch.float32)
+    _same_device("nearest_resize", "in", inp, out=out)
+    _check(load().ada_nearest_resize_fwd(pi, B, hi, wi, out.shape[1], out.shape[2], po, _stream()), "ada_nearest_resize_fwd")
 
 
 def depth_render(depth, lut, ho, wo, out=None, out_u16=None, *, minmax=None, vmin=0.0, vmax=1.0, mask=None, thickness=2, outline_rgb=0,
@@ -699,8 +407,7 @@ def depth_render(depth, lut, ho, wo, out=None, out_u16=None, *, minmax=None, vmi
             continue
         if not isinstance(t, torch.Tensor) or not t.is_contiguous() or t.numel() < need:
             raise HipExtError(f"depth_render: {name} must be a contiguous tensor of at least {need} elements, got {tuple(getattr(t, 'shape', ()))}")
-        if t.device != depth.device:
-            raise HipExtError(f"depth_render: {name} on {t.device}, depth on {depth.device}")
+    _same_device("depth_render", "depth", depth, lut=lut, mask=mask, minmax=minmax, out=out, out_u16=out_u16)
     if mask is not None and mask.shape != depth.shape:
         raise HipExtError(f"depth_render: mask {tuple(mask.shape)} does not match depth {tuple(depth.shape)}")
     _check(load().ada_depth_render_fwd(_dev(depth, "depth", torch.float32), B, hi, wi, _opt(minmax, "minmax", torch.float32), float(vmin), float(vmax),
@@ -720,7 +427,7 @@ def pil_resize_u8(src, batch, hi, wi, channels, row_pitch, image_stride, ho, wo,
         if t is not None and (not isinstance(t, torch.Tensor) or not t.is_contiguous() or t.numel() != need):
             raise HipExtError(f"pil_resize_u8: {name} must be a contiguous tensor of {need} elements, got {tuple(getattr(t, 'shape', ()))}")
     _check_src_extent("pil_resize_u8", src, (batch - 1) * image_stride + (hi - 1) * row_pitch + wi * channels)
-    ptrs = []
+    ptrs, others = [], dict(tmp=tmp, out_u8=out_u8, out_f32=out_f32, out_mask=out_mask)
     for axis, tab, n_out in (("x", tables_x, wo), ("y", tables_y, ho)):
         if tab is None:
             ptrs += [None, None, 0]
@@ -729,9 +436,12 @@ def pil_resize_u8(src, batch, hi, wi, channels, row_pitch, image_stride, ho, wo,
         if bounds.numel() != 2 * n_out or kk.numel() != n_out * ksize or not (bounds.is_contiguous() and kk.is_contiguous()):
             raise HipExtError(f"pil_resize_u8: tables_{axis} must be contiguous [{n_out}, 2] and [{n_out}, {ksize}], got {tuple(bounds.shape)} {tuple(kk.shape)}")
         ptrs += [_dev(bounds, f"bounds_{axis}", torch.int32), _dev(kk, f"kk_{axis}", torch.int32), int(ksize)]
-    _check(load().ada_pil_resize_u8_fwd(_dev(src, "src", torch.uint8), batch, hi, wi, channels, row_pitch, image_stride, ho, wo, int(filter), *ptrs,
-                                        _opt(tmp, "tmp", torch.uint8), tmp.numel() if tmp is not None else 0, _opt(out_u8, "out_u8", torch.uint8),
-                                        _opt(out_f32, "out_f32", torch.float32), _opt(out_mask, "out_mask", torch.uint8), _stream()), "ada_pil_resize_u8_fwd")
+        others.update({f"bounds_{axis}": bounds, f"kk_{axis}": kk})
+    ps, pt, pu = _dev(src, "src", torch.uint8), _opt(tmp, "tmp", torch.uint8), _opt(out_u8, "out_u8", torch.uint8)
+    pf, pm = _opt(out_f32, "out_f32", torch.float32), _opt(out_mask, "out_mask", torch.uint8)
+    _same_device("pil_resize_u8", "src", src, **others)
+    _check(load().ada_pil_resize_u8_fwd(ps, batch, hi, wi, channels, row_pitch, image_stride, ho, wo, int(filter), *ptrs, pt, tmp.numel() if tmp is not None else 0,
+                                        pu, pf, pm, _stream()), "ada_pil_resize_u8_fwd")
 
 
 def label_combine(whole, occ, whole_mask, scale_shift, out_u16, out_f32=None, out_of_range=None, overflow=LABEL_WRAP):
@@ -745,8 +455,9 @@ def label_combine(whole, occ, whole_mask, scale_shift, out_u16, out_f32=None, ou
                            ("out_u16", out_u16, (P, ho, wo)), ("out_f32", out_f32, (P, h, w)), ("out_of_range", out_of_range, (P, ho))):
         if t is None and name in ("out_f32", "out_of_range"):
             continue
-        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or not t.is_contiguous() or t.device != whole.device:
-            raise HipExtError(f"label_combine: {name} must be a contiguous {shape} tensor on {whole.device}, got {tuple(getattr(t, 'shape', ()))}")
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or not t.is_contiguous():
+            raise HipExtError(f"label_combine: {name} must be a contiguous {shape} tensor, got {tuple(getattr(t, 'shape', ()))}")
+    _same_device("label_combine", "whole", whole, occ=occ, whole_mask=whole_mask, scale_shift=scale_shift, out_u16=out_u16, out_f32=out_f32, out_of_range=out_of_range)
     _check(load().ada_label_combine_fwd(_dev(whole, "whole", torch.float32), _dev(occ, "occ", torch.float32), _dev(whole_mask, "whole_mask", torch.uint8),
                                         _dev(scale_shift, "scale_shift", torch.float32), P, h, w, ho, wo, int(overflow), _dev(out_u16, "out_u16", torch.uint16),
                                         _opt(out_f32, "out_f32", torch.float32), _opt(out_of_range, "out_of_range", torch.int32), _stream()),
@@ -763,27 +474,6 @@ def mask_keep_area_workspace_bytes(batch: int, h: int, w: int) -> int:
     return 4 * batch * (h * w // 2 + 2)
 
 
-def _label_map(who, labels):
-    if not isinstance(labels, torch.Tensor) or labels.dim() != 3 or not labels.is_contiguous():
-        raise HipExtError(f"{who}: labels must be a contiguous int32 [K, h, w] tensor, got {tuple(getattr(labels, 'shape', ()))}")
-    _dev(labels, "labels", torch.int32)
-    return tuple(labels.shape)
-
-
-def _sized(who, name, t, shape, dtype):
-    if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
-        raise HipExtError(f"{who}: {name} must be a contiguous {tuple(shape)} tensor, got {tuple(getattr(t, 'shape', ()))}")
-    return _dev(t, name, dtype)
-
-
-def _bytes_of(who, workspace, need, device):
-    if workspace is None:
-        workspace = torch.empty((need + 3) // 4, dtype=torch.int32, device=device)
-    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous() or workspace.device != device:
-        raise HipExtError(f"{who}: workspace must be a contiguous tensor on {device}")
-    return workspace, workspace.numel() * workspace.element_size()
-
-
 def mask_label(src, batch, h, w, row_pitch, image_stride, connectivity, labels, n_labels, workspace=None):
     """uint8 masks [batch][h][w] (rows ``row_pitch`` bytes, images ``image_stride`` bytes apart; non-zero = inside) -> labels int32 [batch, h, w] (0 =
     background, components 1 .. n in the raster order of their first pixels) and n_labels int32 [batch] (ada_mask_label_fwd).  ``workspace``: any
@@ -792,27 +482,29 @@ def mask_label(src, batch, h, w, row_pitch, image_stride, connectivity, labels, 
     _check_src_extent(who, src, (batch - 1) * image_stride + (h - 1) * row_pitch + w)
     pl, pn = _sized(who, "labels", labels, (batch, h, w), torch.int32), _sized(who, "n_labels", n_labels, (batch,), torch.int32)
     ws, ws_bytes = _bytes_of(who, workspace, mask_label_workspace_bytes(batch, h, w), labels.device)
-    _check(load().ada_mask_label_fwd(_dev(src, "src", torch.uint8), batch, h, w, row_pitch, image_stride, int(connectivity), pl, pn, ws.data_ptr(), ws_bytes,
-                                     _stream()), "ada_mask_label_fwd")
+    ps = _dev(src, "src", torch.uint8)
+    _same_device(who, "labels", labels, src=src, n_labels=n_labels)
+    _check(load().ada_mask_label_fwd(ps, batch, h, w, row_pitch, image_stride, int(connectivity), pl, pn, ws.data_ptr(), ws_bytes, _stream()), "ada_mask_label_fwd")
 
 
 def mask_stats(labels, max_labels, stats, sums):
     """labels int32 [K, h, w] -> stats int32 [K, max_labels + 1, 5] (LEFT, TOP, WIDTH, HEIGHT, AREA) and sums int64 [K, max_labels + 1, 2] = (sum x, sum y);
     row 0 is the background, rows without pixels are zero, labels above max_labels are ignored (ada_mask_stats_fwd)."""
-    K, h, w = _label_map("mask_stats", labels)
+    K, h, w = _maps3("mask_stats", labels, "labels", torch.int32)
     ps = _sized("mask_stats", "stats", stats, (K, max_labels + 1, 5), torch.int32)
     pm = _sized("mask_stats", "sums", sums, (K, max_labels + 1, 2), torch.int64)
+    _same_device("mask_stats", "labels", labels, stats=stats, sums=sums)
     _check(load().ada_mask_stats_fwd(labels.data_ptr(), K, h, w, int(max_labels), ps, pm, _stream()), "ada_mask_stats_fwd")
 
 
 def mask_keep_area(labels, min_area, out_u8=None, out_f32=None, workspace=None):
     """labels int32 [K, h, w] -> out_u8 uint8 / out_f32 fp32 0 / 1 [K, h, w] = label != 0 and area(label) >= min_area (ada_mask_keep_area_fwd)."""
     who = "mask_keep_area"
-    K, h, w = _label_map(who, labels)
+    K, h, w = _maps3(who, labels, "labels", torch.int32)
     if out_u8 is None and out_f32 is None:
         raise HipExtError(f"{who}: out_u8 and out_f32 are both None")
-    pu = None if out_u8 is None else _sized(who, "out_u8", out_u8, (K, h, w), torch.uint8)
-    pf = None if out_f32 is None else _sized(who, "out_f32", out_f32, (K, h, w), torch.float32)
+    pu = _like(who, "out_u8", out_u8, labels, torch.uint8, optional=True)
+    pf = _like(who, "out_f32", out_f32, labels, torch.float32, optional=True)
     ws, ws_bytes = _bytes_of(who, workspace, mask_keep_area_workspace_bytes(K, h, w), labels.device)
     _check(load().ada_mask_keep_area_fwd(labels.data_ptr(), K, h, w, int(min_area), pu, pf, ws.data_ptr(), ws_bytes, _stream()), "ada_mask_keep_area_fwd")
 
@@ -821,12 +513,13 @@ def mask_grid_points(labels, stats, small_component_thresh, grid_step, hit):
     """labels int32 [K, h, w], stats int32 [K, cap + 1, 5] -> hit int32 [K, h, w]: the label at the grid points of the components of at least
     ``small_component_thresh`` pixels, 0 elsewhere (ada_mask_grid_points_fwd)."""
     who = "mask_grid_points"
-    K, h, w = _label_map(who, labels)
+    K, h, w = _maps3(who, labels, "labels", torch.int32)
     if not isinstance(stats, torch.Tensor) or stats.dim() != 3 or stats.shape[0] != K or stats.shape[1] < 1 or stats.shape[2] != 5 or not stats.is_contiguous():
         raise HipExtError(f"{who}: stats must be a contiguous int32 [{K}, cap + 1, 5] tensor, got {tuple(getattr(stats, 'shape', ()))}")
-    ph = _sized(who, "hit", hit, (K, h, w), torch.int32)
-    _check(load().ada_mask_grid_points_fwd(labels.data_ptr(), _dev(stats, "stats", torch.int32), K, h, w, stats.shape[1] - 1, int(small_component_thresh),
-                                           int(grid_step), ph, _stream()), "ada_mask_grid_points_fwd")
+    ps, ph = _dev(stats, "stats", torch.int32), _like(who, "hit", hit, labels, torch.int32)
+    _same_device(who, "labels", labels, stats=stats)
+    _check(load().ada_mask_grid_points_fwd(labels.data_ptr(), ps, K, h, w, stats.shape[1] - 1, int(small_component_thresh), int(grid_step), ph, _stream()),
+           "ada_mask_grid_points_fwd")
 
 
 def quantile_workspace_bytes(batch: int) -> int:
@@ -851,14 +544,8 @@ def quantile_select(x, q, out, out_f32=None, count=None, valid=None, mode=Q_NUMP
     po = _sized(who, "out", out, (B, nq), torch.float64)
     pf = None if out_f32 is None else _sized(who, "out_f32", out_f32, (B, nq), torch.float32)
     pc = None if count is None else _sized(who, "count", count, (B,), torch.int64)
-    pv = None
-    if valid is not None:
-        if not isinstance(valid, torch.Tensor) or valid.shape != x.shape or not valid.is_contiguous() or valid.device != x.device:
-            raise HipExtError(f"{who}: valid must be a contiguous uint8 {tuple(x.shape)} tensor on {x.device}, got {tuple(getattr(valid, 'shape', ()))}")
-        pv = _dev(valid, "valid", torch.uint8)
-    for name, t in (("out", out), ("out_f32", out_f32), ("count", count)):
-        if t is not None and t.device != x.device:
-            raise HipExtError(f"{who}: {name} on {t.device}, x on {x.device}")
+    pv = _like(who, "valid", valid, x, torch.uint8, optional=True)
+    _same_device(who, "x", x, out=out, out_f32=out_f32, count=count)
     ws, ws_bytes = _bytes_of(who, workspace, quantile_workspace_bytes(B), x.device)
     _check(load().ada_quantile_fwd(px, pv, B, n, (c_double * nq)(*qs), nq, int(mode), int(flags), float(exclude_value), po, pf, pc, ws.data_ptr(), ws_bytes,
                                    _stream()), "ada_quantile_fwd")
@@ -874,13 +561,6 @@ def mesh_compact_workspace_bytes(batch: int, h: int, w: int) -> int:
     return 4 * batch * (h * w + (h * w + GEOM_CHUNK - 1) // GEOM_CHUNK)
 
 
-def _depth_maps(who, depth):
-    if not isinstance(depth, torch.Tensor) or depth.dim() != 3 or not depth.is_contiguous():
-        raise HipExtError(f"{who}: depth must be a contiguous fp32 [B, h, w] tensor, got {tuple(getattr(depth, 'shape', ()))}")
-    _dev(depth, "depth", torch.float32)
-    return tuple(depth.shape)
-
-
 def _z_rule(inverse):
     return (0, 0.0, 0.0) if inverse is None else (1, float(inverse[0]), float(inverse[1]))
 
@@ -889,7 +569,7 @@ def depth_points(depth, camera, out_f64=None, out_f32=None, valid=None, inverse=
     """depth fp32 [B, h, w] -> points [B, h, w, 3] as fp64 and / or fp32 and optionally valid uint8 [B, h, w] (ada_depth_points_fwd).  ``camera``: 21
     host doubles, Kinv row-major, R row-major, t.  ``inverse``: None for z = depth, (a, b) for z = 1 / (a depth + b)."""
     who = "depth_points"
-    B, h, w = _depth_maps(who, depth)
+    B, h, w = _maps3(who, depth, "depth")
     cam = [float(v) for v in camera]
     if len(cam) != 21:
         raise HipExtError(f"{who}: camera must hold 21 doubles (Kinv, R, t), got {len(cam)}")
@@ -897,7 +577,8 @@ def depth_points(depth, camera, out_f64=None, out_f32=None, valid=None, inverse=
         raise HipExtError(f"{who}: one of out_f64 / out_f32 is needed")
     p64 = None if out_f64 is None else _sized(who, "out_f64", out_f64, (B, h, w, 3), torch.float64)
     p32 = None if out_f32 is None else _sized(who, "out_f32", out_f32, (B, h, w, 3), torch.float32)
-    pv = None if valid is None else _sized(who, "valid", valid, (B, h, w), torch.uint8)
+    pv = _like(who, "valid", valid, depth, torch.uint8, optional=True)
+    _same_device(who, "depth", depth, out_f64=out_f64, out_f32=out_f32)
     inv, a, b = _z_rule(inverse)
     _check(load().ada_depth_points_fwd(depth.data_ptr(), B, h, w, (c_double * 21)(*cam), inv, a, b, p64, p32, pv, _stream()), "ada_depth_points_fwd")
 
@@ -918,9 +599,10 @@ def mesh_triangles(batch, h, w, triangles, count, mask=None, row_pitch=0, image_
         _check_src_extent(who, mask, (batch - 1) * image_stride + (h - 1) * row_pitch + w)
     pd = None
     if depth is not None:
-        if _depth_maps(who, depth) != (batch, h, w):
+        if _maps3(who, depth, "depth") != (batch, h, w):
             raise HipExtError(f"{who}: depth must be [{batch}, {h}, {w}], got {tuple(depth.shape)}")
         pd = depth.data_ptr()
+    _same_device(who, "triangles", triangles, count=count, mask=mask, depth=depth)
     inv, a, b = _z_rule(inverse)
     ws, ws_bytes = _bytes_of(who, workspace, mesh_triangles_workspace_bytes(batch, h, w), triangles.device)
     _check(load().ada_mesh_triangles_fwd(pm, int(row_pitch), int(image_stride), pd, inv, a, b, float(max_ratio), batch, h, w, pt, triangles.shape[1], pc,
@@ -949,6 +631,7 @@ def mesh_compact(triangles, count, h, w, points, points_out, vertex_count, color
         raise HipExtError(f"{who}: colors and colors_out come together")
     pci = None if colors is None else _sized(who, "colors", colors, (B, h * w, 3), torch.uint8)
     pco = None if colors_out is None else _sized(who, "colors_out", colors_out, (B, vcap, 3), torch.uint8)
+    _same_device(who, "triangles", triangles, count=count, points=points, points_out=points_out, vertex_count=vertex_count, colors=colors, colors_out=colors_out)
     ws, ws_bytes = _bytes_of(who, workspace, mesh_compact_workspace_bytes(B, h, w), triangles.device)
     _check(load().ada_mesh_compact_fwd(pt, pc, cap, B, h, w, pp, points.element_size(), pci, po, pco, vcap, pv, ws.data_ptr(), ws_bytes, _stream()),
            "ada_mesh_compact_fwd")
@@ -971,9 +654,7 @@ def mesh_project(points, camera, x, y, w, pose=False):
     if len(cam) != 16:
         raise HipExtError(f"{who}: camera must hold 16 doubles (fx, fy, cx, cy, R, t), got {len(cam)}")
     px, py, pw = _sized(who, "x", x, (V,), torch.int32), _sized(who, "y", y, (V,), torch.int32), _sized(who, "w", w, (V,), torch.float64)
-    for name, t in (("x", x), ("y", y), ("w", w)):
-        if t.device != points.device:
-            raise HipExtError(f"{who}: {name} on {t.device}, points on {points.device}")
+    _same_device(who, "points", points, x=x, y=y, w=w)
     _check(load().ada_mesh_project_fwd(pp, points.element_size(), V, (c_double * 16)(*cam), 1 if pose else 0, px, py, pw, _stream()), "ada_mesh_project_fwd")
 
 
@@ -996,9 +677,7 @@ def mesh_raster(x, y, w, triangles, h, width, depth, index, colors=None, color=N
         raise HipExtError(f"{who}: a color output needs the vertex colors")
     pci = None if colors is None else _sized(who, "colors", colors, (V, 3), torch.uint8)
     pco = None if color is None else _sized(who, "color", color, (h, width, 3), torch.uint8)
-    for name, t in (("y", y), ("w", w), ("triangles", triangles), ("index", index), ("colors", colors), ("color", color), ("x", x)):
-        if t is not None and t.device != depth.device:
-            raise HipExtError(f"{who}: {name} on {t.device}, depth on {depth.device}")
+    _same_device(who, "depth", depth, y=y, w=w, triangles=triangles, index=index, colors=colors, color=color, x=x)
     a, b = (1.0, 0.0) if inverse is None else (float(inverse[0]), float(inverse[1]))
     rgb = [int(c) for c in fill_color]
     if len(rgb) != 3 or min(rgb) < 0 or max(rgb) > 255:
@@ -1016,10 +695,9 @@ def range_map(depth, range32, out, scale=1.0, shift=0.0, clip=None):
         raise HipExtError(f"{who}: depth must be a non-empty contiguous fp32 [B, ...] tensor, got {tuple(getattr(depth, 'shape', ()))}")
     B = depth.shape[0]
     pd = _dev(depth, "depth", torch.float32)
-    po = _sized(who, "out", out, tuple(depth.shape), torch.float32)
+    po = _like(who, "out", out, depth, torch.float32)
     pr = _sized(who, "range32", range32, (B, 2), torch.float32)
-    if out.device != depth.device or range32.device != depth.device:
-        raise HipExtError(f"{who}: depth on {depth.device}, out on {out.device}, range32 on {range32.device}")
+    _same_device(who, "depth", depth, range32=range32)
     lo, hi = (float(clip[0]), float(clip[1])) if clip is not None else (0.0, 0.0)
     _check(load().ada_range_map_fwd(pd, pr, B, depth.numel() // B, float(scale), float(shift), int(clip is not None), lo, hi, po, _stream()), "ada_range_map_fwd")
 
@@ -1029,19 +707,14 @@ def depth_colorize(value, lut, out, range64=None, vmin=0.0, vmax=1.0, invalid_ma
     ``range64`` (device fp64 [B, 2]) when given, else the host numbers vmin / vmax; ``lut`` uint8 [256, 4] R, G, B, A; invalid pixels (``invalid_mask``
     uint8 [B, h, w] non-zero when given, else value == invalid_val) get ``background`` (R, G, B, A bytes).  All contiguous, one device."""
     who = "depth_colorize"
-    if not isinstance(value, torch.Tensor) or value.dim() != 3 or not value.is_contiguous() or value.numel() == 0:
-        raise HipExtError(f"{who}: value must be a non-empty contiguous fp32 [B, h, w] tensor, got {tuple(getattr(value, 'shape', ()))}")
-    B, h, w = value.shape
-    pv = _dev(value, "value", torch.float32)
+    B, h, w = _maps3(who, value, "value")
     pl = _sized(who, "lut", lut, (256, 4), torch.uint8)
     po = _sized(who, "out", out, (B, h, w, 4), torch.uint8)
     pr = None if range64 is None else _sized(who, "range64", range64, (B, 2), torch.float64)
-    pm = None if invalid_mask is None else _sized(who, "invalid_mask", invalid_mask, (B, h, w), torch.uint8)
-    for name, t in (("lut", lut), ("out", out), ("range64", range64), ("invalid_mask", invalid_mask)):
-        if t is not None and t.device != value.device:
-            raise HipExtError(f"{who}: {name} on {t.device}, value on {value.device}")
+    pm = _like(who, "invalid_mask", invalid_mask, value, torch.uint8, optional=True)
+    _same_device(who, "value", value, lut=lut, out=out, range64=range64)
     r, g, b, a = (int(c) & 0xff for c in background)
-    _check(load().ada_depth_colorize_fwd(pv, B, h, w, pr, float(vmin), float(vmax), pl, pm, float(invalid_val), r | (g << 8) | (b << 16) | (a << 24), po,
+    _check(load().ada_depth_colorize_fwd(value.data_ptr(), B, h, w, pr, float(vmin), float(vmax), pl, pm, float(invalid_val), r | (g << 8) | (b << 16) | (a << 24), po,
                                          _stream()), "ada_depth_colorize_fwd")
 
 
@@ -1059,22 +732,6 @@ def edt_workspace_bytes(batch: int, h: int, w: int) -> int:
 def edge_sums_workspace_bytes(batch: int, columns: int = 4) -> int:
     """Bytes of workspace ada_edge_metric_fwd (4 columns) / ada_soft_edge_fwd (2 columns) ask for."""
     return 8 * batch * EDGE_SUM_BLOCKS * columns
-
-
-def _maps3(who, first, name="image", dtype=torch.float32):
-    if not isinstance(first, torch.Tensor) or first.dim() != 3 or not first.is_contiguous() or first.numel() == 0:
-        raise HipExtError(f"{who}: {name} must be a non-empty contiguous [B, h, w] tensor, got {tuple(getattr(first, 'shape', ()))}")
-    _dev(first, name, dtype)
-    return tuple(first.shape)
-
-
-def _like(who, name, t, ref, dtype, optional=False):
-    if t is None and optional:
-        return None
-    p = _sized(who, name, t, tuple(ref.shape), dtype)
-    if t.device != ref.device:
-        raise HipExtError(f"{who}: {name} on {t.device}, expected {ref.device}")
-    return p
 
 
 def canny_front(image, weights, low_threshold, low_masked, pre=CANNY_PRE_NONE, pre_out=None, smoothed=None, isobel=None, jsobel=None, magnitude=None):
@@ -1120,6 +777,7 @@ def edge_metric_sums(pred_edges, gt_edges, valid, d_target, d_pred, th_acc, sums
     pv = _like(who, "valid", valid, pred_edges, torch.uint8, optional=True)
     pt, pp = _like(who, "d_target", d_target, pred_edges, torch.float64), _like(who, "d_pred", d_pred, pred_edges, torch.float64)
     ps = _sized(who, "sums", sums, (B, 4), torch.float64)
+    _same_device(who, "pred_edges", pred_edges, sums=sums)
     ws, ws_bytes = _bytes_of(who, workspace, edge_sums_workspace_bytes(B, 4), pred_edges.device)
     _check(load().ada_edge_metric_fwd(pred_edges.data_ptr(), pg, pv, pt, pp, B, h, w, float(th_acc), ps, ws.data_ptr(), ws_bytes, _stream()),
            "ada_edge_metric_fwd")
@@ -1133,6 +791,7 @@ def soft_edge(pred, gt, valid, radius, sums, workspace=None):
     pg = _like(who, "gt", gt, pred, torch.float32)
     pv = _like(who, "valid", valid, pred, torch.uint8, optional=True)
     ps = _sized(who, "sums", sums, (B, 2), torch.float64)
+    _same_device(who, "pred", pred, sums=sums)
     ws, ws_bytes = _bytes_of(who, workspace, edge_sums_workspace_bytes(B, 2), pred.device)
     _check(load().ada_soft_edge_fwd(pred.data_ptr(), pg, pv, B, h, w, int(radius), ps, ws.data_ptr(), ws_bytes, _stream()), "ada_soft_edge_fwd")
 

@@ -11,13 +11,14 @@ raises HipExtError.
 """
 from __future__ import annotations
 
-from collections import OrderedDict, namedtuple
+from collections import namedtuple
 
 import numpy as np
 import torch
 
 from . import (CANNY_MAX_RADIUS, CANNY_PRE_LOG, CANNY_PRE_LOG15, CANNY_PRE_NONE, SOFT_EDGE_MAX_RADIUS, HipExtError, canny_front, canny_hysteresis, edge_metric_sums,
                edt, soft_edge)
+from ._staging import DeviceCache, check_planar, resolve_device, stage_planar
 
 _PRE = {None: CANNY_PRE_NONE, "none": CANNY_PRE_NONE, "log": CANNY_PRE_LOG, "log1.5": CANNY_PRE_LOG15}
 
@@ -40,66 +41,18 @@ def gaussian_weights(sigma: float) -> np.ndarray:
     return phi / phi.sum()
 
 
-_WEIGHTS = OrderedDict()      # (sigma, device) -> fp64 device tensor
-_WEIGHTS_MAX = 16
+_WEIGHTS = DeviceCache(16)      # (sigma, device) -> fp64 device tensor
 
 
 def _device_weights(sigma, device):
-    key = (float(sigma), device)
-    t = _WEIGHTS.get(key)
-    if t is None:
-        t = torch.from_numpy(gaussian_weights(sigma)).to(device)
-        _WEIGHTS[key] = t
-        while len(_WEIGHTS) > _WEIGHTS_MAX:
-            _WEIGHTS.popitem(last=False)
-    else:
-        _WEIGHTS.move_to_end(key)
-    return t
-
-
-def _device_of(x, device, who):
-    if device is None:
-        if isinstance(x, torch.Tensor):
-            device = x.device
-        elif torch.cuda.is_available():
-            device = torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device) if device is not None else None
-    if device is None or device.type != "cuda":
-        raise HipExtError(f"{who}: target device {device} is not a HIP device (the HIP path has no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    return device
+    return _WEIGHTS.get((float(sigma), device), lambda: torch.from_numpy(gaussian_weights(sigma)).to(device))
 
 
 def _stage(x, device, who, name, dtypes):
     """The checked map as a contiguous device tensor [B, h, w] of dtypes[0] (bool is viewed as uint8) and whether the caller gave [h, w]."""
-    if isinstance(x, np.ndarray):
-        ok = x.dtype in tuple(np.dtype(str(d).replace("torch.", "")) for d in dtypes)
-    elif isinstance(x, torch.Tensor):
-        ok = x.dtype in dtypes
-    else:
-        raise TypeError(f"{who}: {name}: expected a numpy array or a torch tensor, got {type(x).__name__}")
-    if not ok:
-        raise TypeError(f"{who}: {name}: expected {' or '.join(str(d).replace('torch.', '') for d in dtypes)}, got {x.dtype}")
-    if x.ndim not in (2, 3) or min(x.shape) < 1:
-        raise ValueError(f"{who}: {name}: expected [h, w] or [B, h, w], got shape {tuple(x.shape)}")
-    device = _device_of(x, device, who)
-    if isinstance(x, np.ndarray):
-        t = torch.from_numpy(np.ascontiguousarray(x).copy()).to(device)
-    else:
-        if x.device != device:
-            raise HipExtError(f"{who}: {name} on {x.device}, expected it on the HIP device {device}")
-        t = x
-    single = t.dim() == 2
-    if single:
-        t = t[None]
-    B, h, w = t.shape
-    if h * w >= 2 ** 31 or B > 65535:
-        raise ValueError(f"{who}: h * w must stay below 2^31 and B within 65535, got {tuple(t.shape)}")
-    t = t.contiguous()
-    if t.dtype == torch.bool:
-        t = t.view(torch.uint8)
-    return t, single
+    single = check_planar(who, x, dtypes, f"{name}: expected")
+    device = resolve_device(who, device, x)
+    return stage_planar(who, x, device, name).contiguous(), single      # these kernels take no pitch
 
 
 def _same(who, name, t, ref):

@@ -23,7 +23,7 @@ import torch
 
 from . import (HipExtError, RASTER_OUT_NORMALISED, RASTER_OUT_W, RASTER_OUT_Z, depth_points, mesh_compact, mesh_project, mesh_raster,
                mesh_raster_workspace_bytes, mesh_triangles)
-from .image import _as_int
+from ._staging import as_int, check_planar, from_numpy, resolve_device, stage_planar
 
 Mesh = namedtuple("Mesh", "points triangles vertex_count triangle_count colors")
 Mesh.__doc__ = """One image's mesh on the device: points [vertex_count, 3] (fp32 or fp64), triangles int32 [triangle_count, 3] indexing them, the two counts as
@@ -46,7 +46,7 @@ def get_intrinsics(h, w, fov_deg=55.0) -> np.ndarray:
 
 
 def _grid(who, h, w):
-    hw = _as_int(h), _as_int(w)
+    hw = as_int(h), as_int(w)
     if None in hw or min(hw) < 1:
         raise ValueError(f"{who}: h and w must be positive integers, got {h!r} x {w!r}")
     if hw[0] * hw[1] >= MAX_PIXELS:
@@ -54,83 +54,31 @@ def _grid(who, h, w):
     return hw
 
 
-def _device_of(who, device, *arrays):
-    for a in arrays:
-        if device is None and isinstance(a, torch.Tensor):
-            device = a.device
-    if device is None and torch.cuda.is_available():
-        device = torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device) if device is not None else None
-    if device is None or device.type != "cuda":
-        raise HipExtError(f"{who}: target device {device} is not a HIP device (the HIP path has no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    return device
+def _check_planar(who, x, dtypes, name):
+    """Shape and type of a depth or mask argument, before any device is looked at: whether it is [h, w]."""
+    was2d = check_planar(who, x, dtypes, f"{name} must be")
+    if not was2d and x.shape[0] > 65535:
+        raise ValueError(f"{who}: {name}: at most 65535 per call, got {x.shape[0]}")
+    return was2d
 
 
 def _check_depth(who, depth):
-    """Shape and type of a depth argument, before any device is looked at: (h, w, was_2d)."""
-    if isinstance(depth, np.ndarray):
-        ok = depth.dtype == np.float32
-    elif isinstance(depth, torch.Tensor):
-        ok = depth.dtype == torch.float32
-    else:
-        raise TypeError(f"{who}: depth must be a numpy array or a torch tensor, got {type(depth).__name__}")
-    if not ok:
-        raise TypeError(f"{who}: depth must be float32, got {depth.dtype}")
-    if depth.ndim not in (2, 3) or min(depth.shape) < 1:
-        raise ValueError(f"{who}: depth must be [h, w] or [B, h, w], got shape {tuple(depth.shape)}")
-    h, w = _grid(who, depth.shape[-2], depth.shape[-1])
-    if depth.ndim == 3 and depth.shape[0] > 65535:
-        raise ValueError(f"{who}: at most 65535 maps per call, got {depth.shape[0]}")
-    return h, w, depth.ndim == 2
-
-
-def _from_numpy(a):
-    a = np.ascontiguousarray(a)
-    return torch.from_numpy(a if a.flags.writeable else a.copy())      # a decoded image is a read-only view; the tensor only feeds a copy to the device
-
-
-def _stage_depth(who, depth, device):
-    if isinstance(depth, np.ndarray):
-        d = _from_numpy(depth).to(device)
-    else:
-        if depth.device != device:
-            raise HipExtError(f"{who}: depth on {depth.device}, expected it on the HIP device {device}")
-        d = depth.contiguous()
-    return d[None] if d.dim() == 2 else d
+    """(h, w, was_2d) of a checked depth argument."""
+    was2d = _check_planar(who, depth, (torch.float32,), "depth")
+    return _grid(who, depth.shape[-2], depth.shape[-1]) + (was2d,)
 
 
 def _check_mask(who, mask):
-    if isinstance(mask, np.ndarray):
-        ok = mask.dtype in (np.uint8, np.bool_)
-    elif isinstance(mask, torch.Tensor):
-        ok = mask.dtype in (torch.uint8, torch.bool)
-    else:
-        raise TypeError(f"{who}: mask must be a numpy array or a torch tensor, got {type(mask).__name__}")
-    if not ok:
-        raise TypeError(f"{who}: mask must be uint8 or bool, got {mask.dtype}")
-    if mask.ndim not in (2, 3) or min(mask.shape) < 1:
-        raise ValueError(f"{who}: mask must be [h, w] or [B, h, w], got shape {tuple(mask.shape)}")
-    if mask.ndim == 3 and mask.shape[0] > 65535:
-        raise ValueError(f"{who}: at most 65535 masks per call, got {mask.shape[0]}")
-    return mask.ndim == 2
+    return _check_planar(who, mask, (torch.uint8, torch.bool), "mask")
+
+
+def _stage_depth(who, depth, device):
+    return stage_planar(who, depth, device, "depth").contiguous()      # the kernels take no pitch for a depth map
 
 
 def _stage_mask(who, mask, device):
     """uint8 device tensor [B, h, w] whose rows are packed and whose pitches the kernel can walk: a crop stays a view."""
-    if isinstance(mask, np.ndarray):
-        m = torch.from_numpy(np.ascontiguousarray(mask).view(np.uint8).copy()).to(device)
-    else:
-        if mask.device != device:
-            raise HipExtError(f"{who}: mask on {mask.device}, expected it on the HIP device {device}")
-        m = mask
-    if m.dim() == 2:
-        m = m[None]
-    B, h, w = m.shape
-    if not (m.stride(2) == 1 and m.stride(1) >= w and (B == 1 or m.stride(0) >= (h - 1) * m.stride(1) + w)):
-        m = m.contiguous()
-    return m.view(torch.uint8) if m.dtype == torch.bool else m
+    return stage_planar(who, mask, device, "mask")
 
 
 def _camera(who, h, w, R, t, K, fov_deg):
@@ -175,7 +123,7 @@ def depth_to_points(depth, R=None, t=None, K=None, fov_deg=55.0, inverse=None, d
         raise ValueError(f"{who}: dtype must be torch.float64 or torch.float32, got {dtype!r}")
     cam = _camera(who, h, w, R, t, K, fov_deg)
     inverse = _inverse(who, inverse)
-    device = _device_of(who, device, depth)
+    device = resolve_device(who, device, depth)
     with torch.cuda.device(device):
         d = _stage_depth(who, depth, device)
         out = torch.empty(d.shape + (3,), dtype=dtype, device=device)
@@ -208,7 +156,7 @@ def create_triangles(h, w, mask=None, depth=None, inverse=None, max_ratio=None, 
     h, w = _grid(who, h, w)
     cap = None
     if capacity is not None:
-        cap = _as_int(capacity)
+        cap = as_int(capacity)
         if cap is None or cap < 0 or cap >= 2 ** 31:
             raise ValueError(f"{who}: capacity must be an integer >= 0, got {capacity!r}")
     single = True
@@ -226,7 +174,7 @@ def create_triangles(h, w, mask=None, depth=None, inverse=None, max_ratio=None, 
             raise ValueError(f"{who}: mask {tuple(mask.shape)} and depth {tuple(depth.shape)} differ in shape")
     inverse = _inverse(who, inverse)
     ratio = _ratio(who, max_ratio, depth)
-    device = _device_of(who, device, mask, depth)
+    device = resolve_device(who, device, mask, depth)
     with torch.cuda.device(device):
         m = None if mask is None else _stage_mask(who, mask, device)
         d = None if depth is None else _stage_depth(who, depth, device)
@@ -243,7 +191,7 @@ def _stage_colors(who, colors, h, w, device):
     if colors is None:
         return None
     if isinstance(colors, np.ndarray):
-        colors = _from_numpy(colors).to(device)
+        colors = from_numpy(colors).to(device)
     if not isinstance(colors, torch.Tensor) or colors.dtype != torch.uint8 or tuple(colors.shape) != (h, w, 3):
         raise ValueError(f"{who}: colors must be uint8 [{h}, {w}, 3], got {getattr(colors, 'dtype', type(colors).__name__)} {tuple(getattr(colors, 'shape', ()))}")
     if colors.device != device:
@@ -264,7 +212,7 @@ def depth_to_mesh(depth, mask=None, colors=None, compact=True, R=None, t=None, K
         raise ValueError(f"{who}: one map [h, w] per call, got shape {tuple(depth.shape)}")
     if mask is not None and (not _check_mask(who, mask) or tuple(mask.shape) != (h, w)):
         raise ValueError(f"{who}: mask must be [{h}, {w}], got shape {tuple(mask.shape)}")
-    device = _device_of(who, device, depth, mask)
+    device = resolve_device(who, device, depth, mask)
     with torch.cuda.device(device):
         d = _stage_depth(who, depth, device)[0]
         col = _stage_colors(who, colors, h, w, device)
@@ -312,7 +260,7 @@ def amodal_layers(result, image=None, near=1.0, far=10.0, fov_deg=55.0, max_rati
         colors = None
         if image is not None:
             from .image import resize_nearest
-            img = _from_numpy(image) if isinstance(image, np.ndarray) else image
+            img = from_numpy(image) if isinstance(image, np.ndarray) else image
             if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] < 3:
                 raise ValueError(f"{who}: image must be uint8 [h, w, 3] in B, G, R order")
             planes = img.to(base.device)[:, :, :3].permute(2, 0, 1).float().contiguous()
@@ -399,7 +347,7 @@ def _check_part(who, points, triangles, colors):
 
 def _stage_part(who, a, device):
     if isinstance(a, np.ndarray):
-        return _from_numpy(a).to(device)
+        return from_numpy(a).to(device)
     if a.device != device:
         raise HipExtError(f"{who}: a mesh tensor on {a.device}, expected it on the HIP device {device}")
     return a.contiguous()
@@ -419,7 +367,7 @@ def _render(who, parts, labels, h, w, K, fov_deg, R, t, out, inverse, fill, fill
     if len({str(p[0].dtype).replace("torch.", "") for p in parts}) > 1:
         raise ValueError(f"{who}: the meshes' points must share one type")
     with_color = all(p[2] is not None for p in parts)      # colours are rendered when every mesh has them
-    device = _device_of(who, device, *[a for p in parts for a in p])
+    device = resolve_device(who, device, *[a for p in parts for a in p])
     with torch.cuda.device(device):
         staged = [tuple(None if a is None else _stage_part(who, a, device) for a in p) for p in parts]
         if len(staged) == 1:
@@ -496,7 +444,7 @@ def render_layers(layers, h, w, objects=None, scene=True, near=1.0, far=10.0, ou
         raise TypeError(f"{who}: a Layers expected, got {type(layers).__name__}")
     if not (near > 0 and far > near):
         raise ValueError(f"{who}: 0 < near < far expected, got near={near!r} far={far!r}")
-    chosen = list(range(len(layers.objects))) if objects is None else [_as_int(k) for k in objects]
+    chosen = list(range(len(layers.objects))) if objects is None else [as_int(k) for k in objects]
     if any(k is None or not 0 <= k < len(layers.objects) for k in chosen):
         raise ValueError(f"{who}: objects must index the {len(layers.objects)} object meshes, got {objects!r}")
     meshes = ([layers.scene] if scene else []) + [layers.objects[k] for k in chosen]

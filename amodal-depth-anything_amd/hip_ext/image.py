@@ -17,12 +17,11 @@ draw_mask_outline), not cv2.findContours / drawContours: there is no cv2 here to
 """
 from __future__ import annotations
 
-import operator
-
 import numpy as np
 import torch
 
 from . import HipExtError, depth_colorize, depth_render, depth_resize, image_prep, mask_prep, nearest_resize, photo_prep
+from ._staging import DeviceCache, as_int, check_planar, resolve_device, stage_hwc, stage_planar, with_index
 
 PIXEL_MEAN = (0.485, 0.456, 0.406)
 PIXEL_STD = (0.229, 0.224, 0.225)
@@ -66,16 +65,8 @@ def _stage_image(img, device, who):
     """The checked photo as a uint8 [h, w, c] tensor on ``device`` with packed pixels: numpy is copied, a device tensor is read in place at its
     own row stride (made contiguous only when its pixels are not packed).  Returns (tensor, device)."""
     _check_image(img)
-    device = torch.device(device) if device is not None else None
-    if device is None or device.type != "cuda":
-        raise HipExtError(f"{who}: target device {device} is not a HIP device (the HIP path has no CPU fallback)")
-    if isinstance(img, np.ndarray):
-        return torch.from_numpy(np.ascontiguousarray(img)).to(device), device
-    if img.device != device:
-        raise HipExtError(f"{who}: image on {img.device}, expected it on the HIP device {device}")
-    c = img.shape[2]
-    packed = img.stride(2) == 1 and img.stride(1) == c and img.stride(0) >= img.shape[1] * c
-    return (img if packed else img.contiguous()), device
+    device = resolve_device(who, device, current=False)      # the caller names the device: the model's
+    return stage_hwc(who, img, device), device
 
 
 def image_to_tensor(img, input_size: int = 518, device=None):
@@ -92,18 +83,8 @@ def image_to_tensor(img, input_size: int = 518, device=None):
     return out, (h, w)
 
 
-def _as_int(v):
-    """Any integer type (int, a numpy integer, a 0-d integer tensor) as a Python int; None for anything else, bool included."""
-    if isinstance(v, bool):
-        return None
-    try:
-        return operator.index(v)
-    except TypeError:
-        return None
-
-
 def _check_size(size, who) -> int:
-    s = _as_int(size)
+    s = as_int(size)
     if s is None or s < 14 or s % 14:
         raise ValueError(f"{who}: size must be a positive multiple of 14 (the patch size), got {size!r}")
     return s
@@ -128,33 +109,11 @@ def masks_to_tensor(masks, size: int, device, guide: bool = False):
     """``masks``: uint8 or bool [h, w] or [K, h, w] (numpy array, copied; or a torch tensor on ``device``, read in place when its rows are
     packed); any non-zero value is inside.  Returns mask01 fp32 0/1 [K, 1, size, size] on ``device``: F.interpolate(mode="nearest") > 0, the
     mask of reference infer.py:86-87.  guide=True: (mask01, 2 * mask01 - 1), the second being the network's guide_mask (infer.py:91)."""
-    if isinstance(masks, np.ndarray):
-        dtype_ok = masks.dtype in (np.uint8, np.bool_)
-    elif isinstance(masks, torch.Tensor):
-        dtype_ok = masks.dtype in (torch.uint8, torch.bool)
-    else:
-        raise TypeError(f"masks: expected a numpy array or a torch tensor, got {type(masks).__name__}")
-    if not dtype_ok:
-        raise TypeError(f"masks: expected uint8 or bool, got {masks.dtype}")
-    if masks.ndim not in (2, 3) or min(masks.shape) < 1:
-        raise ValueError(f"masks: expected [h, w] or [K, h, w], got shape {tuple(masks.shape)}")
+    check_planar("masks", masks, (torch.uint8, torch.bool))
     size = _check_size(size, "masks_to_tensor")
-    device = torch.device(device) if device is not None else None
-    if device is None or device.type != "cuda":
-        raise HipExtError(f"masks_to_tensor: target device {device} is not a HIP device (the HIP path has no CPU fallback)")
-    if isinstance(masks, np.ndarray):
-        src = torch.from_numpy(np.ascontiguousarray(masks).view(np.uint8)).to(device)
-    else:
-        if masks.device != device:
-            raise HipExtError(f"masks_to_tensor: masks on {masks.device}, expected them on the HIP device {device}")
-        src = masks
-    if src.dim() == 2:
-        src = src[None]
+    device = resolve_device("masks_to_tensor", device, current=False)
+    src = stage_planar("masks_to_tensor", masks, device, "masks", limits=False)
     K, h, w = src.shape
-    if not (src.stride(2) == 1 and src.stride(1) >= w and (K == 1 or src.stride(0) >= (h - 1) * src.stride(1) + w)):
-        src = src.contiguous()
-    if src.dtype == torch.bool:
-        src = src.view(torch.uint8)     # one byte per element, 0 / 1: same strides
     mask01 = torch.empty(K, 1, size, size, dtype=torch.float32, device=device)
     pm1 = torch.empty_like(mask01) if guide else None
     with torch.cuda.device(device):
@@ -179,7 +138,7 @@ def resize_nearest(depth: torch.Tensor, h: int, w: int) -> torch.Tensor:
     photo's size with (infer.py:77, 113)."""
     if not isinstance(depth, torch.Tensor) or depth.dim() != 3 or depth.dtype != torch.float32:
         raise HipExtError(f"resize_nearest: expected fp32 [B, H, W], got {getattr(depth, 'dtype', type(depth).__name__)} {tuple(getattr(depth, 'shape', ()))}")
-    hw = _as_int(h), _as_int(w)
+    hw = as_int(h), as_int(w)
     if None in hw or min(hw) < 1:
         raise ValueError(f"resize_nearest: the target size must be two positive integers, got {h!r} x {w!r}")
     h, w = hw
@@ -190,41 +149,32 @@ def resize_nearest(depth: torch.Tensor, h: int, w: int) -> torch.Tensor:
     return out
 
 
-_LUTS = {}
+_LUTS = DeviceCache(64)      # (name, device[, "rgba"]) -> uint8 table on the device
+
+
+def _colormap(who, cmap):
+    import matplotlib
+    cm = matplotlib.colormaps[cmap]
+    if cm.N != 256:
+        raise ValueError(f"{who}: colour map {cmap!r} has {cm.N} entries, the renderer needs 256")
+    return cm
 
 
 def colormap_lut(cmap: str = "Spectral_r", device=None) -> torch.Tensor:
     """The 256 colours of a matplotlib colour map as uint8 [256, 3] (R, G, B) on ``device``: (cmap(i)[:3] * 255).astype(uint8), the table
     ada_depth_render_fwd indexes with min((int)(t * 256), 255).  Cached per (name, device).  A map that does not have 256 entries is refused:
     the index rule assumes them."""
-    import matplotlib
-    cm = matplotlib.colormaps[cmap]
-    if cm.N != 256:
-        raise ValueError(f"colormap_lut: colour map {cmap!r} has {cm.N} entries, the renderer needs 256")
-    device = torch.device(device) if device is not None else torch.device("cpu")
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (cmap, device)
-    if key not in _LUTS:
-        table = (cm(np.arange(256))[:, :3] * 255).astype(np.uint8)
-        _LUTS[key] = torch.from_numpy(np.ascontiguousarray(table)).to(device)
-    return _LUTS[key]
+    cm = _colormap("colormap_lut", cmap)
+    device = with_index("cpu" if device is None else device)
+    return _LUTS.get((cmap, device), lambda: torch.from_numpy(np.ascontiguousarray((cm(np.arange(256))[:, :3] * 255).astype(np.uint8))).to(device))
 
 
 def colormap_lut_rgba(cmap: str = "turbo_r", device=None) -> torch.Tensor:
     """The 256 colours of a matplotlib colour map as uint8 [256, 4] (R, G, B, A) on ``device``: cmap(arange(256), bytes=True), the table
     ada_depth_colorize_fwd indexes.  Cached per (name, device); a map without 256 entries is refused, as by colormap_lut."""
-    import matplotlib
-    cm = matplotlib.colormaps[cmap]
-    if cm.N != 256:
-        raise ValueError(f"colormap_lut_rgba: colour map {cmap!r} has {cm.N} entries, the renderer needs 256")
-    device = torch.device(device) if device is not None else torch.device("cpu")
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    key = (cmap, device, "rgba")
-    if key not in _LUTS:
-        _LUTS[key] = torch.from_numpy(np.ascontiguousarray(cm(np.arange(256), bytes=True))).to(device)
-    return _LUTS[key]
+    cm = _colormap("colormap_lut_rgba", cmap)
+    device = with_index("cpu" if device is None else device)
+    return _LUTS.get((cmap, device, "rgba"), lambda: torch.from_numpy(np.ascontiguousarray(cm(np.arange(256), bytes=True))).to(device))
 
 
 def colorize(value, vmin=None, vmax=None, cmap="turbo_r", invalid_val=-99, invalid_mask=None, background_color=(128, 128, 128, 255), gamma_corrected=False,
@@ -250,7 +200,7 @@ def colorize(value, vmin=None, vmax=None, cmap="turbo_r", invalid_val=-99, inval
     value = value.contiguous()
     B, H, W = value.shape
     dev = value.device
-    bg = tuple(_as_int(v) for v in background_color) if isinstance(background_color, (tuple, list)) and len(background_color) == 4 else (None,)
+    bg = tuple(as_int(v) for v in background_color) if isinstance(background_color, (tuple, list)) and len(background_color) == 4 else (None,)
     if None in bg or not all(0 <= v <= 255 for v in bg):
         raise ValueError(f"{who}: background_color must be four bytes (R, G, B, A), got {background_color!r}")
     mask = None
@@ -296,14 +246,14 @@ def render_depth(depth, masks=None, out_size=None, cmap="Spectral_r", vmin=0.0, 
     if out_size is None:
         h, w = H, W
     else:
-        hw = tuple(_as_int(v) for v in out_size) if isinstance(out_size, (tuple, list)) and len(out_size) == 2 else (None, None)
+        hw = tuple(as_int(v) for v in out_size) if isinstance(out_size, (tuple, list)) and len(out_size) == 2 else (None, None)
         if None in hw or min(hw) < 1:
             raise ValueError(f"render_depth: out_size must be None or two positive integers (h, w), got {out_size!r}")
         h, w = hw
-    t = _as_int(thickness)
+    t = as_int(thickness)
     if t is None or not 1 <= t <= 4:
         raise ValueError(f"render_depth: thickness must be 1..4, got {thickness!r}")
-    rgb = tuple(_as_int(v) for v in outline) if isinstance(outline, (tuple, list)) and len(outline) == 3 else (None,)
+    rgb = tuple(as_int(v) for v in outline) if isinstance(outline, (tuple, list)) and len(outline) == 3 else (None,)
     if None in rgb or not all(0 <= v <= 255 for v in rgb):
         raise ValueError(f"render_depth: outline must be three bytes (R, G, B), got {outline!r}")
     if not 0.0 <= float(alpha) <= 1.0:

@@ -12,13 +12,15 @@ integer arithmetic bit for bit (ada_pil_resize_u8_fwd); the coefficient tables a
 from __future__ import annotations
 
 import math
-from collections import OrderedDict, namedtuple
+from collections import namedtuple
 
 import numpy as np
 import torch
 
 from . import (FIT_SCALE, FIT_SHIFT, LABEL_CLIP, LABEL_WRAP, PIL_BICUBIC, PIL_NEAREST, HipExtError, label_combine, minmax, normalize, pil_resize_u8,
                protocol_fit)
+from ._args import _u8
+from ._staging import DeviceCache, as_int, check_planar, resolve_device, stage_hwc, stage_planar
 
 _PRECISION_BITS = 22      # Pillow's Resample.c: 32 - 8 - 2
 _FILTERS = {"bicubic": PIL_BICUBIC, "nearest": PIL_NEAREST}
@@ -51,71 +53,28 @@ def pil_coeffs(n_in: int, n_out: int):
     return np.stack([xmin, n], axis=1).astype(np.int32), np.ascontiguousarray(q.astype(np.int32)), ksize
 
 
-_TABLES = OrderedDict()      # (n_in, n_out, device) -> (bounds, kk, ksize) on the device
-_TABLES_MAX = 64
+_TABLES = DeviceCache(64)      # (n_in, n_out, device) -> (bounds, kk, ksize) on the device
 
 
 def _device_tables(n_in, n_out, device):
-    key = (n_in, n_out, device)
-    tab = _TABLES.get(key)
-    if tab is None:
+    def make():
         bounds, kk, ksize = pil_coeffs(n_in, n_out)
-        tab = (torch.from_numpy(bounds).to(device), torch.from_numpy(kk).to(device), ksize)
-        _TABLES[key] = tab
-        while len(_TABLES) > _TABLES_MAX:
-            _TABLES.popitem(last=False)
-    else:
-        _TABLES.move_to_end(key)
-    return tab
-
-
-def _as_device(device, img, who):
-    if device is None:
-        if isinstance(img, torch.Tensor):
-            device = img.device
-        elif torch.cuda.is_available():
-            device = torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device) if device is not None else None
-    if device is None or device.type != "cuda":
-        raise HipExtError(f"{who}: target device {device} is not a HIP device (the HIP path has no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    return device
+        return torch.from_numpy(bounds).to(device), torch.from_numpy(kk).to(device), ksize
+    return _TABLES.get((n_in, n_out, device), make)
 
 
 def _stage(img, device, who):
-    """The checked pixels as (uint8 device tensor, K, h, w, channels, row pitch, image stride, kind) with kind in {"l", "rgb", "stack"}: the staging of
-    hip_ext.image._stage_image -- numpy is copied, a device tensor is read in place at its own strides when its pixels are packed -- and its errors."""
-    if isinstance(img, np.ndarray):
-        dtype_ok = img.dtype == np.uint8
-    elif isinstance(img, torch.Tensor):
-        dtype_ok = img.dtype == torch.uint8
-    else:
-        raise TypeError(f"{who}: expected a numpy array or a torch tensor, got {type(img).__name__}")
-    if not dtype_ok:
-        raise TypeError(f"{who}: expected uint8 pixels, got {img.dtype}")
-    if img.ndim not in (2, 3) or min(img.shape) < 1:
-        raise ValueError(f"{who}: expected [h, w], [h, w, 3] or [K, h, w], got shape {tuple(img.shape)}")
-    device = _as_device(device, img, who)
-    if isinstance(img, np.ndarray):
-        arr = np.ascontiguousarray(img)
-        src = torch.from_numpy(arr if arr.flags.writeable else arr.copy()).to(device)      # np.asarray(PIL image) is read-only: torch wants a writable one
-    else:
-        if img.device != device:
-            raise HipExtError(f"{who}: image on {img.device}, expected it on the HIP device {device}")
-        src = img
-    if src.dim() == 3 and src.shape[2] == 3:          # [h, w, 3]: a last axis of three is RGB, never a stack of masks three pixels wide
+    """The checked pixels as (uint8 device tensor, K, h, w, channels, row pitch, image stride, kind) with kind in {"l", "rgb", "stack"}: numpy is
+    copied, a device tensor is read in place at its own strides when its pixels are packed ([h, w], [h, w, 3] or [K, h, w])."""
+    single = check_planar(who, img, (torch.uint8,), shapes="[h, w], [h, w, 3] or [K, h, w]")
+    device = resolve_device(who, device, img)
+    if img.ndim == 3 and img.shape[2] == 3:          # [h, w, 3]: a last axis of three is RGB, never a stack of masks three pixels wide
+        src = stage_hwc(who, img, device)
         h, w, _ = src.shape
-        if not (src.stride(2) == 1 and src.stride(1) == 3 and src.stride(0) >= 3 * w):
-            src = src.contiguous()
         return src, 1, h, w, 3, src.stride(0), h * src.stride(0), "rgb"
-    kind = "l" if src.dim() == 2 else "stack"
-    if src.dim() == 2:
-        src = src[None]
+    src = stage_planar(who, img, device, "image", limits=False)
     K, h, w = src.shape
-    if not (src.stride(2) == 1 and src.stride(1) >= w and (K == 1 or src.stride(0) >= (h - 1) * src.stride(1) + w)):
-        src = src.contiguous()
-    return src, K, h, w, 1, src.stride(1), src.stride(0), kind
+    return src, K, h, w, 1, src.stride(1), src.stride(0), "l" if single else "stack"
 
 
 def _resize_into(staged, ho, wo, filt, device, out_u8=None, out_f32=None, out_mask=None):
@@ -131,8 +90,7 @@ def _resize_into(staged, ho, wo, filt, device, out_u8=None, out_f32=None, out_ma
 
 
 def _check_hw(size_hw, who):
-    from .image import _as_int
-    hw = tuple(_as_int(v) for v in size_hw) if isinstance(size_hw, (tuple, list)) and len(size_hw) == 2 else (None, None)
+    hw = tuple(as_int(v) for v in size_hw) if isinstance(size_hw, (tuple, list)) and len(size_hw) == 2 else (None, None)
     if None in hw or min(hw) < 1:
         raise ValueError(f"{who}: the target size must be two positive integers (h, w), got {size_hw!r}")
     return hw
@@ -208,14 +166,12 @@ def label_from_depths(whole_depth, occ_depth, visible_u8, whole_u8, label_size=5
         if not isinstance(m, torch.Tensor) or m.dtype not in (torch.uint8, torch.bool) or m.shape != whole_depth.shape or m.device != whole_depth.device:
             raise HipExtError(f"{who}: {name} must be uint8 {tuple(whole_depth.shape)} on {whole_depth.device}, got "
                               f"{getattr(m, 'dtype', type(m).__name__)} {tuple(getattr(m, 'shape', ()))}")
-        m = m.contiguous()
-        masks.append(m.view(torch.uint8) if m.dtype == torch.bool else m)
+        masks.append(_u8(m.contiguous()))
     visible, whole_mask = masks
     if label_size is None:
         ho, wo = h, w
     else:
-        from .image import _as_int
-        ho = wo = _as_int(label_size)
+        ho = wo = as_int(label_size)
         if ho is None or ho < 1:
             raise ValueError(f"{who}: label_size must be None or a positive integer, got {label_size!r}")
     dev = whole_depth.device
@@ -257,7 +213,7 @@ def pseudo_label_pairs(model_raw, whole_images, occ_images, visible_masks, whole
     if P < 1 or not (len(occ_images) == len(visible_masks) == len(whole_masks) == P):
         raise ValueError(f"{who}: {P} photos, {len(occ_images)} composites, {len(visible_masks)} visible and {len(whole_masks)} whole masks: one of each per pair")
     resample = _per_item(mask_resample, P, who)
-    device = _as_device(next(model_raw.parameters()).device, None, who)
+    device = resolve_device(who, next(model_raw.parameters()).device)
     x = torch.empty(2 * P, 3, size, size, dtype=torch.float32, device=device)
     masks = torch.empty(2, P, size, size, dtype=torch.uint8, device=device)
     for i in range(P):

@@ -12,11 +12,10 @@ from __future__ import annotations
 
 from collections import namedtuple
 
-import numpy as np
 import torch
 
-from . import HipExtError, mask_grid_points, mask_keep_area, mask_label, mask_stats
-from .image import _as_int
+from . import mask_grid_points, mask_keep_area, mask_label, mask_stats
+from ._staging import as_int, check_planar, resolve_device, stage_planar
 
 Components = namedtuple("Components", "labels count stats centroids")
 Components.__doc__ = """Device tensors of connected_components: labels int32 [K, h, w] (0 = background), count int32 [K] (components per mask), stats int32
@@ -25,14 +24,14 @@ Components.__doc__ = """Device tensors of connected_components: labels int32 [K,
 
 
 def _connectivity(who, connectivity):
-    c = _as_int(connectivity)
+    c = as_int(connectivity)
     if c not in (4, 8):
         raise ValueError(f"{who}: connectivity must be 4 or 8, got {connectivity!r}")
     return c
 
 
 def _non_negative(who, name, v, least=0):
-    i = _as_int(v)
+    i = as_int(v)
     if i is None or i < least or i >= 2 ** 31:
         raise ValueError(f"{who}: {name} must be an integer >= {least}, got {v!r}")
     return i
@@ -40,42 +39,9 @@ def _non_negative(who, name, v, least=0):
 
 def _stage(masks, device, who):
     """The checked masks as (uint8 device tensor [K, h, w] with packed rows, device): masks_to_tensor's staging and errors."""
-    if isinstance(masks, np.ndarray):
-        dtype_ok = masks.dtype in (np.uint8, np.bool_)
-    elif isinstance(masks, torch.Tensor):
-        dtype_ok = masks.dtype in (torch.uint8, torch.bool)
-    else:
-        raise TypeError(f"{who}: expected a numpy array or a torch tensor, got {type(masks).__name__}")
-    if not dtype_ok:
-        raise TypeError(f"{who}: expected uint8 or bool, got {masks.dtype}")
-    if masks.ndim not in (2, 3) or min(masks.shape) < 1:
-        raise ValueError(f"{who}: expected [h, w] or [K, h, w], got shape {tuple(masks.shape)}")
-    if device is None:
-        if isinstance(masks, torch.Tensor):
-            device = masks.device
-        elif torch.cuda.is_available():
-            device = torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device) if device is not None else None
-    if device is None or device.type != "cuda":
-        raise HipExtError(f"{who}: target device {device} is not a HIP device (the HIP path has no CPU fallback)")
-    if device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
-    if isinstance(masks, np.ndarray):
-        src = torch.from_numpy(np.ascontiguousarray(masks).view(np.uint8).copy()).to(device)
-    else:
-        if masks.device != device:
-            raise HipExtError(f"{who}: masks on {masks.device}, expected them on the HIP device {device}")
-        src = masks
-    if src.dim() == 2:
-        src = src[None]
-    K, h, w = src.shape
-    if h * w >= 2 ** 31 or K > 65535:
-        raise ValueError(f"{who}: h * w must stay below 2^31 and K within 65535, got {tuple(src.shape)}")
-    if not (src.stride(2) == 1 and src.stride(1) >= w and (K == 1 or src.stride(0) >= (h - 1) * src.stride(1) + w)):
-        src = src.contiguous()
-    if src.dtype == torch.bool:
-        src = src.view(torch.uint8)     # one byte per element, 0 / 1: same strides
-    return src, device
+    check_planar(who, masks, (torch.uint8, torch.bool))
+    device = resolve_device(who, device, masks)
+    return stage_planar(who, masks, device, "masks"), device
 
 
 def _label(src, connectivity):

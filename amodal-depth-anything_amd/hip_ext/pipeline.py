@@ -93,10 +93,11 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
     guidance for the network and receive pasted depth.  The visible masks are not touched.  None: nothing runs, the call is exactly the one without it.
     render_percentiles: (lo, hi) in [0, 100] -- with render=True each picture is coloured between these percentiles of its own map (colorize()'s range,
     hip_ext.quantile.percentile_range, taken on the device) instead of between 0 and 1.  None: the pictures are exactly the ones without it."""
-    from .image import _as_int, _check_size, masks_to_tensor, photo_to_inputs, render_depth, resize_nearest
+    from ._staging import as_int
+    from .image import _check_size, masks_to_tensor, photo_to_inputs, render_depth, resize_nearest
     size = _check_size(size, "amodal_infer_image")
     if not (out_size is None or (isinstance(out_size, str) and out_size == "image")
-            or (isinstance(out_size, (tuple, list)) and len(out_size) == 2 and all((_as_int(v) or 0) > 0 for v in out_size))):
+            or (isinstance(out_size, (tuple, list)) and len(out_size) == 2 and all((as_int(v) or 0) > 0 for v in out_size))):
         raise ValueError(f"amodal_infer_image: out_size must be None, 'image' or (h, w), got {out_size!r}")
     device = next(amodal_model.parameters()).device
     rgb_raw, rgb, (h, w) = photo_to_inputs(image, size, device)

@@ -12,6 +12,7 @@ from collections import namedtuple
 import torch
 
 from . import (Q_EXCLUDE_VALUE, Q_NUMPY, Q_POSITIVE_ONLY, Q_TORCH, QUANTILE_MAX_Q, HipExtError, quantile_select, quantile_workspace_bytes)
+from ._args import _u8
 
 _METHODS = {"numpy": Q_NUMPY, "torch": Q_TORCH}
 
@@ -24,8 +25,7 @@ def _as_mask(mask, like, who, name):
     if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.uint8, torch.bool) or mask.shape != like.shape or mask.device != like.device:
         raise HipExtError(f"{who}: {name} must be uint8 or bool {tuple(like.shape)} on {like.device}, got "
                           f"{getattr(mask, 'dtype', type(mask).__name__)} {tuple(getattr(mask, 'shape', ()))}")
-    mask = mask.contiguous()
-    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    return _u8(mask.contiguous())
 
 
 def _check_map(x, who, name="x"):

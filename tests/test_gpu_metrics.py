@@ -113,6 +113,21 @@ def test_eval_scale_shift_and_clip_inside_the_kernel(hip):
         assert float(got[k]) == pytest.approx(v, rel=5e-6, abs=1e-9), k
 
 
+def test_eval_packs_a_non_contiguous_bool_mask(hip):
+    """A bool mask that is a crop of a larger tensor is not packed; the kernel reads B * n consecutive bytes, so the wrapper has to hand it a packed
+    copy: the sums equal those of the contiguous mask bit for bit (the same kernel on the same bytes)."""
+    import hip_ext as H
+    pred, gt, mask = _rand(2, 33, 47, seed=11)
+    big = torch.zeros(2, 40, 64, dtype=torch.bool, device="cuda")
+    big[:, 3:36, 5:52] = torch.from_numpy(mask).cuda()
+    crop = big[:, 3:36, 5:52]
+    assert not crop.is_contiguous()
+    p, g = torch.from_numpy(pred).cuda(), torch.from_numpy(gt).cuda()
+    want = H.depth_eval(p, g, crop.contiguous())
+    assert float(want[0, H.EVAL_N]) == float(mask[0].sum()) and float(want[1, H.EVAL_N]) == float(mask[1].sum())
+    assert torch.equal(H.depth_eval(p, g, crop), want)
+
+
 def test_depth2disparity(mods):
     _, alignment = mods
     d = torch.tensor([[0.0, 2.0], [-1.0, 4.0]]).cuda()
