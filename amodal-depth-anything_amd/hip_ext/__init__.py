@@ -687,6 +687,41 @@ def mesh_raster(x, y, w, triangles, h, width, depth, index, colors=None, color=N
                                       ws.data_ptr(), ws_bytes, _stream()), "ada_mesh_raster_fwd")
 
 
+def mesh_adaptive_workspace_bytes(h: int, w: int) -> int:
+    """Bytes of workspace ada_mesh_adaptive_fwd asks for an h x w map, whatever the batch (ada_mesh_adaptive_workspace_bytes)."""
+    n = ctypes.c_int64(0)
+    _check(load().ada_mesh_adaptive_workspace_bytes(int(h), int(w), ctypes.byref(n)), "ada_mesh_adaptive_workspace_bytes")
+    return n.value
+
+
+def mesh_adaptive(batch, h, w, depth, triangles, count, mask=None, row_pitch=0, image_stride=0, inverse=None, max_ratio=0.0, max_error=None, error=None,
+                  error_ready=False, workspace=None):
+    """The error-bounded RTIN mesh of each depth map, rows in heap order (ada_mesh_adaptive_fwd, the contract in include/ada_hip.h): triangles int32
+    [batch, capacity, 3] receives the first min(count, capacity) rows of each image, count int32 [batch] the true number.  ``depth``: contiguous fp32
+    [batch, h, w], ``mask`` / ``inverse`` / ``max_ratio`` as in mesh_triangles.  ``max_error``: the tolerance on the relative disparity error, finite and
+    >= 0, or None for every keepable leaf.  ``error``: optional fp64 [batch, h, w] that receives the error map E; with ``error_ready`` it holds E already (an
+    earlier call on the same map, mask, inverse and max_ratio) and the error phase is skipped.  ``workspace``: at least
+    mesh_adaptive_workspace_bytes(h, w) bytes, 16-byte aligned, allocated when None."""
+    who = "mesh_adaptive"
+    if _maps3(who, depth, "depth") != (batch, h, w):
+        raise HipExtError(f"{who}: depth must be [{batch}, {h}, {w}], got {tuple(depth.shape)}")
+    if not isinstance(triangles, torch.Tensor) or triangles.dim() != 3 or triangles.shape[0] != batch or triangles.shape[2] != 3 or not triangles.is_contiguous():
+        raise HipExtError(f"{who}: triangles must be a contiguous int32 [{batch}, capacity, 3] tensor, got {tuple(getattr(triangles, 'shape', ()))}")
+    pt = _dev(triangles, "triangles", torch.int32)
+    pc = _sized(who, "count", count, (batch,), torch.int32)
+    pm = None
+    if mask is not None:
+        pm = _dev(mask, "mask", torch.uint8)
+        _check_src_extent(who, mask, (batch - 1) * image_stride + (h - 1) * row_pitch + w)
+    pe = None if error is None else _sized(who, "error", error, (batch, h, w), torch.float64)
+    _same_device(who, "depth", depth, triangles=triangles, count=count, mask=mask, error=error)
+    inv, a, b = _z_rule(inverse)
+    ws, ws_bytes = _bytes_of(who, workspace, mesh_adaptive_workspace_bytes(h, w), depth.device)
+    _check(load().ada_mesh_adaptive_fwd(pm, int(row_pitch), int(image_stride), depth.data_ptr(), inv, a, b, float(max_ratio),
+                                        0.0 if max_error is None else float(max_error), 1 if max_error is None else 0, batch, h, w, pt, triangles.shape[1], pc,
+                                        pe, 1 if error_ready else 0, ws.data_ptr(), ws_bytes, _stream()), "ada_mesh_adaptive_fwd")
+
+
 def range_map(depth, range32, out, scale=1.0, shift=0.0, clip=None):
     """out = ((depth - lo) / (hi - lo)) * scale + shift per image, clamped to ``clip`` = (lo, hi) when given; (lo, hi) of the map from ``range32``, device
     fp32 [B, 2] (ada_range_map_fwd).  depth, out: contiguous fp32 [B, ...] of one shape."""

@@ -53,6 +53,11 @@ RASTER_TILE_W, RASTER_TILE_H = 32, 8
 RASTER_WALK_BLOCKS = 2048
 RASTER_WALK_SHARE = 16
 RASTER_OUT_W, RASTER_OUT_Z, RASTER_OUT_NORMALISED = 0, 1, 2
+# ada_mesh_adaptive_fwd: midpoints of a level at or below which the remaining levels share one workgroup, the width of a subtree's cell, the largest
+# side of the virtual grid
+ADAPT_FOLD = 1024
+ADAPT_CELL = 32
+ADAPT_MAX_N = 16384
 # ada_canny_fwd: pre-transforms and the Gaussian's radius cap; ada_soft_edge_fwd's radius cap; partial rows per image and columns of the edge sums
 CANNY_PRE_NONE, CANNY_PRE_LOG, CANNY_PRE_LOG15 = 0, 1, 2
 CANNY_MAX_RADIUS = 16
@@ -152,6 +157,9 @@ PROTOTYPES = {
     "ada_mesh_project_fwd": (c_int, [c_void_p, c_int32, c_int32, POINTER(c_double), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ada_mesh_raster_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_double, c_float,
                                     c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ada_mesh_adaptive_workspace_bytes": (c_int, [c_int32, c_int32, POINTER(c_int64)]),
+    "ada_mesh_adaptive_fwd": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int32, c_double, c_double, c_double, c_double, c_int32, c_int32, c_int32, c_int32,
+                                      c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
     "ada_canny_fwd": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p]),
     "ada_canny_hysteresis_fwd": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_int64, c_void_p]),

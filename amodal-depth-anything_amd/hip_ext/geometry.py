@@ -21,8 +21,8 @@ from collections import namedtuple
 import numpy as np
 import torch
 
-from . import (HipExtError, RASTER_OUT_NORMALISED, RASTER_OUT_W, RASTER_OUT_Z, depth_points, mesh_compact, mesh_project, mesh_raster,
-               mesh_raster_workspace_bytes, mesh_triangles)
+from . import (HipExtError, RASTER_OUT_NORMALISED, RASTER_OUT_W, RASTER_OUT_Z, depth_points, mesh_adaptive, mesh_adaptive_workspace_bytes, mesh_compact,
+               mesh_project, mesh_raster, mesh_raster_workspace_bytes, mesh_triangles)
 from ._staging import as_int, check_planar, from_numpy, resolve_device, stage_planar
 
 Mesh = namedtuple("Mesh", "points triangles vertex_count triangle_count colors")
@@ -187,6 +187,73 @@ def create_triangles(h, w, mask=None, depth=None, inverse=None, max_ratio=None, 
     return out[0] if single else out
 
 
+def _tolerance(who, max_error):
+    if max_error is None:
+        return None
+    try:
+        tau = float(max_error)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: max_error must be None or a number, got {max_error!r}") from None
+    if not (0.0 <= tau < float("inf")):
+        raise ValueError(f"{who}: max_error must be finite and >= 0, got {max_error!r}")
+    return tau
+
+
+@torch.no_grad()
+def adaptive_triangles(depth, mask=None, inverse=None, max_ratio=None, max_error=0.01, capacity=None, return_error=False, device=None):
+    """An adaptive triangle list over a depth map in place of create_triangles' two triangles per cell: a right-triangulated irregular network (the
+    binary tree of right isosceles triangles of terrain meshes), refined until the relative error of the disparity at every hypotenuse midpoint is
+    at most ``max_error`` -- the disparity is ``a depth + b`` with ``inverse=(a, b)`` and 1 / depth otherwise; a plane in space is linear in it.  The
+    mesh is conforming (no T-junction, no crack), wound as create_triangles winds, indexes the same h w vertices (so it feeds mesh_compact and
+    render_mesh unchanged) and keeps only triangles whose finest cover passes create_triangles' tests: inside ``mask``, z finite and > 0,
+    z_max <= ``max_ratio`` z_min.  ``max_error=None``: the finest mesh, every such leaf.  Rows come in the tree's heap order, the same bytes every
+    run; include/ada_hip.h has the contract.  A map whose sides are not 2^k + 1 is refined along its right and bottom borders (a 12 x 19 plane: 82
+    triangles where a 17 x 17 one has 2): the tree spans the enclosing power-of-two square and the vertices outside the map force it.
+
+    depth: fp32 [h, w] or [B, h, w], h, w >= 2, at most 16385 on a side; mask: uint8 / bool of that shape or None.  ``capacity=None``: the counts are
+    read back once and the result is a list of exactly sized int32 [n_b, 3] device tensors, or one tensor for a 2-D depth.  An explicit ``capacity``:
+    (triangles int32 [B, capacity, 3], count int32 [B]) with no host read, as create_triangles.  ``return_error=True`` appends the error map E, fp64
+    [h, w] / [B, h, w] (+inf where a triangle must split whatever the tolerance): E depends on the tolerance not at all, so a sweep reuses it."""
+    who = "adaptive_triangles"
+    h, w, single = _check_depth(who, depth)
+    if min(h, w) < 2:
+        raise ValueError(f"{who}: h and w must be at least 2, got {h} x {w}")
+    cap = None
+    if capacity is not None:
+        cap = as_int(capacity)
+        if cap is None or cap < 0 or cap >= 2 ** 31:
+            raise ValueError(f"{who}: capacity must be an integer >= 0, got {capacity!r}")
+    if mask is not None:
+        m2 = _check_mask(who, mask)
+        if tuple(mask.shape) != tuple(depth.shape) or m2 != single:
+            raise ValueError(f"{who}: mask {tuple(mask.shape)} and depth {tuple(depth.shape)} differ in shape")
+    inverse = _inverse(who, inverse)
+    ratio = _ratio(who, max_ratio, depth)
+    tau = _tolerance(who, max_error)
+    device = resolve_device(who, device, depth, mask)
+    with torch.cuda.device(device):
+        m = None if mask is None else _stage_mask(who, mask, device)
+        d = _stage_depth(who, depth, device)
+        B = d.shape[0]
+        ws = torch.empty((mesh_adaptive_workspace_bytes(h, w) + 15) // 16 * 2, dtype=torch.int64, device=device)
+        count = torch.empty(B, dtype=torch.int32, device=device)
+        kw = dict(mask=m, row_pitch=0 if m is None else m.stride(1), image_stride=0 if m is None else m.stride(0), inverse=inverse, max_ratio=ratio,
+                  max_error=tau, workspace=ws)
+        if cap is not None:
+            tri = torch.empty(B, cap, 3, dtype=torch.int32, device=device)
+            err = torch.empty(B, h, w, dtype=torch.float64, device=device) if return_error else None
+            mesh_adaptive(B, h, w, d, tri, count, error=err, **kw)
+            return (tri, count, err) if return_error else (tri, count)
+        err = torch.empty(B, h, w, dtype=torch.float64, device=device) if tau is not None or return_error else None      # the finest mesh needs no E
+        mesh_adaptive(B, h, w, d, torch.empty(B, 0, 3, dtype=torch.int32, device=device), count, error=err, **kw)
+        counts = count.tolist()      # the one host read
+        tri = torch.empty(B, max(counts), 3, dtype=torch.int32, device=device)
+        mesh_adaptive(B, h, w, d, tri, count, error=err, error_ready=err is not None, **kw)      # the error map is the first call's
+        out = [tri[b, :n] for b, n in enumerate(counts)]
+    out = out[0] if single else out
+    return (out, err[0] if single else err) if return_error else out
+
+
 def _stage_colors(who, colors, h, w, device):
     if colors is None:
         return None
@@ -201,10 +268,12 @@ def _stage_colors(who, colors, h, w, device):
 
 @torch.no_grad()
 def depth_to_mesh(depth, mask=None, colors=None, compact=True, R=None, t=None, K=None, fov_deg=55.0, inverse=None, max_ratio=None,
-                  dtype=torch.float32, device=None) -> Mesh:
+                  dtype=torch.float32, max_error=None, device=None) -> Mesh:
     """One depth map fp32 [h, w] -> a Mesh: depth_to_points, then create_triangles over ``mask`` (uint8 / bool [h, w] or None) with the validity and ratio
     rules applied from the same map.  ``colors``: uint8 [h, w, 3] per vertex, or None.  ``compact=True`` keeps only the vertices a triangle uses, in
     raster order, and renumbers the triangles; False keeps all h w points (invalid ones NaN or behind the camera, used by no triangle).
+    ``max_error``: None is create_triangles' two triangles per cell; a number takes adaptive_triangles' mesh for that tolerance on the relative disparity
+    error instead (h, w >= 2) -- far fewer triangles over flat ground, the same cover, and with compact only the vertices it uses.
     Host reads: the triangle count, and with compact the vertex count."""
     who = "depth_to_mesh"
     h, w, was2d = _check_depth(who, depth)
@@ -217,7 +286,10 @@ def depth_to_mesh(depth, mask=None, colors=None, compact=True, R=None, t=None, K
         d = _stage_depth(who, depth, device)[0]
         col = _stage_colors(who, colors, h, w, device)
         points = depth_to_points(d, R=R, t=t, K=K, fov_deg=fov_deg, inverse=inverse, dtype=dtype, device=device).reshape(1, h * w, 3)
-        tri = create_triangles(h, w, mask=mask, depth=d, inverse=inverse, max_ratio=max_ratio, device=device)
+        if max_error is None:
+            tri = create_triangles(h, w, mask=mask, depth=d, inverse=inverse, max_ratio=max_ratio, device=device)
+        else:
+            tri = adaptive_triangles(d, mask=mask, inverse=inverse, max_ratio=max_ratio, max_error=max_error, device=device)
         n_tri = tri.shape[0]
         if not compact:
             return Mesh(points[0], tri, h * w, n_tri, None if col is None else col[0])
@@ -233,7 +305,7 @@ def depth_to_mesh(depth, mask=None, colors=None, compact=True, R=None, t=None, K
 
 
 @torch.no_grad()
-def amodal_layers(result, image=None, near=1.0, far=10.0, fov_deg=55.0, max_ratio=None) -> Layers:
+def amodal_layers(result, image=None, near=1.0, far=10.0, fov_deg=55.0, max_ratio=None, max_error=None) -> Layers:
     """The layered geometry of an AmodalResult (hip_ext.pipeline.amodal_infer_image): the scene Mesh from ``result.base`` over every pixel and one Mesh per
     object from ``result.blended[k]`` over ``result.masks[k] > 0`` -- the occluded object reconstructed behind its occluder.
 
@@ -241,7 +313,8 @@ def amodal_layers(result, image=None, near=1.0, far=10.0, fov_deg=55.0, max_rati
     v = 1 lies at ``near``, v = 0 at ``far``.  The reference fixes no such mapping.  With far = inf the pixel at v = 0 (``base`` contains one exactly) has
     no finite z: it is an invalid vertex and belongs to no triangle.  ``image``: the photo, uint8 [h, w, 3] in B, G, R order, brought to the maps' size by
     hip_ext.image.resize_nearest's rule, gives the vertex colours (stored R, G, B).  An all-zero mask gives an empty Mesh.  base and blended must have one
-    size (call amodal_infer_image with the same out_size for both, its default)."""
+    size (call amodal_infer_image with the same out_size for both, its default).  ``max_error``: depth_to_mesh's, for every layer -- the error is then
+    measured on the networks' own output, in which the disparity is linear."""
     who = "amodal_layers"
     base, blended, masks = result.base, result.blended, result.masks
     for name, v in (("base", base), ("blended", blended), ("masks", masks)):
@@ -265,7 +338,7 @@ def amodal_layers(result, image=None, near=1.0, far=10.0, fov_deg=55.0, max_rati
                 raise ValueError(f"{who}: image must be uint8 [h, w, 3] in B, G, R order")
             planes = img.to(base.device)[:, :, :3].permute(2, 0, 1).float().contiguous()
             colors = resize_nearest(planes, h, w).flip(0).permute(1, 2, 0).to(torch.uint8).contiguous()      # R, G, B
-        kw = dict(colors=colors, fov_deg=fov_deg, inverse=inverse, max_ratio=max_ratio)
+        kw = dict(colors=colors, fov_deg=fov_deg, inverse=inverse, max_ratio=max_ratio, max_error=max_error)
         scene = depth_to_mesh(base.float(), **kw)
         objects = [depth_to_mesh(blended[k].float(), mask=(masks[k] > 0), **kw) for k in range(blended.shape[0])]
     return Layers(scene, objects)

@@ -2,12 +2,15 @@
 """A depth map in, a triangle mesh out: the reference's ``zoedepth/utils/geometry.py`` (depth_to_points, create_triangles) as a command line.
 
     python -m src.scripts.depth_to_mesh DEPTH OUTPUT.ply [--mask MASK.png] [--inverse NEAR FAR] [--max_ratio R] [--fov 55] [--image PHOTO]
+                                                        [--max_error E]
 
 DEPTH is a 16-bit (or 8-bit) one-channel PNG / TIFF read with Pillow, or a ``.npy`` float array.  Without ``--inverse`` its values are depths, as the
 reference takes them.  With ``--inverse NEAR FAR`` they are normalised inverse depth -- what this project's networks and its 16-bit pseudo-labels hold:
 an integer image is first divided by its type's largest value, and v in [0, 1] becomes z = 1 / (v (1 / NEAR - 1 / FAR) + 1 / FAR).  The unprojection,
 the triangle selection (inside MASK, valid depth, and with ``--max_ratio`` no triangle whose farthest vertex is more than R times its nearest) and the
-vertex compaction run on the device (hip_ext.geometry); the PLY is written on the host.
+vertex compaction run on the device (hip_ext.geometry); the PLY is written on the host.  ``--max_error E`` writes an adaptive mesh in place of two
+triangles per pixel cell: conforming right triangles refined until the relative disparity error at every split point is at most E
+(hip_ext.geometry.adaptive_triangles) -- 0.01 keeps a few per cent of the triangles of a smooth map.
 """
 import argparse
 import os
@@ -45,7 +48,7 @@ def read_mask(path, shape) -> np.ndarray:
     return np.ascontiguousarray((m > 0).astype(np.uint8))
 
 
-def mesh_file(src, dst, mask=None, inverse=None, max_ratio=None, fov=55.0, image=None, device="cuda"):
+def mesh_file(src, dst, mask=None, inverse=None, max_ratio=None, fov=55.0, image=None, device="cuda", max_error=None):
     """Meshes one file; returns the hip_ext.geometry.Mesh that was written."""
     depth = read_depth(src, normalise=inverse is not None)
     ab = None
@@ -60,7 +63,7 @@ def mesh_file(src, dst, mask=None, inverse=None, max_ratio=None, fov=55.0, image
         if colors.shape[:2] != depth.shape:
             raise ValueError(f"{image}: photo of shape {colors.shape[:2]} for a depth map of shape {depth.shape}")
     mesh = geometry.depth_to_mesh(depth, mask=None if mask is None else read_mask(mask, depth.shape), colors=colors, fov_deg=fov, inverse=ab,
-                                  max_ratio=max_ratio, device=device)
+                                  max_ratio=max_ratio, max_error=max_error, device=device)
     os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)
     geometry.write_ply(dst, mesh)
     return mesh
@@ -75,9 +78,10 @@ def main(argv=None):
     ap.add_argument("--max_ratio", type=float, default=None, help="drop triangles whose farthest vertex is more than this many times their nearest")
     ap.add_argument("--fov", type=float, default=55.0, help="field of view of the pinhole camera in degrees")
     ap.add_argument("--image", default=None, help="a photo of the depth map's size for the vertex colours")
+    ap.add_argument("--max_error", type=float, default=None, help="adaptive mesh: the largest relative disparity error of a triangle that is not split (default: two triangles per cell)")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
-    mesh = mesh_file(args.input, args.output, args.mask, args.inverse, args.max_ratio, args.fov, args.image, args.device)
+    mesh = mesh_file(args.input, args.output, args.mask, args.inverse, args.max_ratio, args.fov, args.image, args.device, args.max_error)
     print(f"{args.output}: {mesh.vertex_count} vertices, {mesh.triangle_count} triangles")
     return 0
 

@@ -771,6 +771,62 @@ int ada_mesh_raster_fwd(const int32_t* x, const int32_t* y, const double* w, con
                         float* depth, int32_t* index, uint8_t* color, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Adaptive depth-map meshes: an error-bounded right-triangulated irregular network (RTIN: the binary tree of right isosceles triangles of
+ * Lindstrom's and "martini"-style terrain meshes) in place of ada_mesh_triangles_fwd's two triangles per cell (csrc/ada_adaptive.hip).  The reference
+ * has no such mesh: the arithmetic is the library's own, tests/_adaptive_ref.py restates it in numpy and the GPU suite compares bit for bit.  Additions
+ * under ABI 10.  The mesh is conforming by construction (no T-junction, no crack, no skirt).  The launch sequence depends on the shapes and the flags
+ * alone, nothing is read back or allocated: legal inside a stream capture.  The file is built without floating-point contraction.
+ *   GRID.  A map of h x w vertices, h, w >= 2.  N is the smallest power of two with N >= max(h, w) - 1 (N <= ADA_ADAPT_MAX_N, else ADA_EUNSUPPORTED);
+ *     the virtual grid is (N + 1) x (N + 1).  A vertex (i, j) = (row, column) with i >= h or j >= w is ABSENT.  A vertex's id in the output is i w + j,
+ *     the ids of ada_mesh_triangles_fwd: ada_mesh_compact_fwd works on the result unchanged.
+ *   TREE.  A triangle is (a, b, c), right angle at c, hypotenuse a b, m = (a + b) / 2.  Roots ((N, N), (0, 0), (N, 0)) then ((0, 0), (N, N), (0, N)).
+ *     Children of (a, b, c): left (c, a, m), right (b, c, m); they keep the parent's winding, which with these roots is that of ada_mesh_triangles_fwd's
+ *     (tl, bl, tr).  Heap index: roots 2 and 3, children 2 t and 2 t + 1.  Level 0 holds the roots; the leaves (legs of length 1) are level
+ *     2 log2 N: 2 log2 N + 1 levels, 2 N^2 leaves.
+ *   DISPARITY.  omega(v), fp64: inverse == 1: a * (double)depth + b, the product and the sum rounded once each (what ada_depth_points_fwd forms before
+ *     its reciprocal); inverse == 0: 1.0 / (double)depth.  The error is measured on omega, not on z: a plane in space is linear in omega over the
+ *     pixel grid, omega is what ada_mesh_raster_fwd interpolates, and with inverse == 1 it is linear in the network's output.
+ *   KEEPABLE LEAF.  Its three vertices are present and pass the tests ada_mesh_triangles_fwd applies to a candidate's three vertices: inside the mask,
+ *     valid (z finite and > 0, the z rule above), and with max_ratio > 0 z_max <= max_ratio * z_min.
+ *   ERROR MAP.  E, fp64 per vertex, initially 0.  Triangles bottom-up by level; for a non-leaf T
+ *       F(T) = +inf                                          if T's children are leaves and one of them is not keepable
+ *       F(T) = max(|0.5 (omega_a + omega_b) - omega_m| / omega_m,   the sum, the product, the difference and the quotient each rounded once
+ *                  E[m(left child)], E[m(right child)])             (the last two only when the children are not leaves)
+ *       E[m(T)] = max(E[m(T)], F(T))
+ *     over the up to two triangles that share m as hypotenuse midpoint: both sides of a hypotenuse split together.  +inf travels upwards through the
+ *     child terms; the quotient is evaluated only where the child terms are finite (every vertex of T is then valid and omega_m finite and positive),
+ *     so E holds no NaN.  E is monotone along the tree.  A triangle that touches an absent vertex has F = +inf.
+ *   EMISSION for the tolerance tau = max_error (finite, >= 0).  A non-leaf T is a row iff (T is a root or E[m(parent)] > tau) and E[m(T)] <= tau.
+ *     A leaf is a row iff (it is a root or E[m(parent)] > tau) and it is keepable.  no_max_error == 1: every keepable leaf (2 (h - 1) (w - 1) rows
+ *     without a mask on a valid map).  A plane on a (2^k + 1)^2 map is 2 rows; a map whose sides are not 2^k + 1 refines along the image border
+ *     because the absent vertices force it (a 12 x 19 plane: 82 rows) -- the price of one conforming root square.
+ *   ORDER.  Ascending heap index; a row is (id(a), id(b), id(c)), int32.
+ *   ada_mesh_adaptive_workspace_bytes   *bytes = what ada_mesh_adaptive_fwd asks for an h x w map (any batch: images run one after the other)
+ *   ada_mesh_adaptive_fwd
+ *     mask       optional uint8 [batch][h][w], rows row_pitch_bytes apart, images image_stride_bytes apart, as ada_mesh_triangles_fwd
+ *     depth      fp32 [batch][h][w] packed
+ *     triangles  int32 [batch][capacity][3]: the first min(count, capacity) rows of each image; rows from count on are untouched
+ *     count      int32 [batch] on the device: the true number, also when it exceeds capacity (the overflow signal)
+ *     error_out  optional fp64 [batch][h][w]: receives E.  error_ready == 1: it HOLDS E already, from an earlier call with the same depth, mask, inverse
+ *                rule and max_ratio, and the error phase is skipped -- for callers who sweep the tolerance or size the output from a first count
+ *     workspace  the caller's, 16-byte aligned, workspace_bytes >= ada_mesh_adaptive_workspace_bytes (checked)
+ *     Work: E by a gather per midpoint vertex (each vertex is the midpoint of one level only), one launch per level while the level holds more than
+ *     ADA_ADAPT_FOLD midpoints inside the image, the coarser levels in one workgroup; emission by one predicate and a count / scan / write
+ *     compaction in heap order over the subtrees below the cells of ADA_ADAPT_CELL vertices' width that overlap the image, the levels above them
+ *     walked by one workgroup.  No subtree wholly outside the image is launched over.  E is monotone along the tree, so a subtree whose root's
+ *     parent is not split has no row and is left at once.  No atomic decides a position or a value (the one LDS add is an integer count): the same
+ *     bytes every run.
+ * ---------------------------------------------------------------------------------------- */
+#define ADA_ADAPT_FOLD 1024           /* midpoints of a level at or below which the remaining levels run in one workgroup */
+#define ADA_ADAPT_CELL 32             /* width of the cells whose two halves are the subtrees of the emission's workgroups */
+#define ADA_ADAPT_MAX_N 16384         /* largest side of the virtual grid */
+int ada_mesh_adaptive_workspace_bytes(int32_t h, int32_t w, int64_t* bytes);
+int ada_mesh_adaptive_fwd(const uint8_t* mask, int64_t row_pitch_bytes, int64_t image_stride_bytes, const float* depth, int32_t inverse, double a,
+                          double b, double max_ratio, double max_error, int32_t no_max_error, int32_t batch, int32_t h, int32_t w,
+                          int32_t* triangles, int32_t capacity, int32_t* count, double* error_out, int32_t error_ready, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * The edge metrics of the reference's evaluation (reference src/util/metric.py:181-328), which the reference computes on the host with
  * skimage.feature.canny and scipy.ndimage.distance_transform_edt after copying two full-size maps per sample.  Additions under ABI 10.  All maps are
  * packed [batch][h][w]; h * w < 2^31, batch <= 65535, h and w down to 1.  No atomics of their own (ada_canny_hysteresis_fwd runs ada_mask_label_fwd, whose
