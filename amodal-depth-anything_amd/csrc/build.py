@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)     # isa_guard.py lives next to this file: the package builds without the repository's tools/
-SOURCES = ["ada_api.hip", "ada_igemm.hip", "ada_attention.hip", "ada_elementwise.hip", "ada_pipeline.hip", "ada_eval.hip", "ada_tail.hip", "ada_image.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip", "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip"]
+SOURCES = ["ada_api.hip", "ada_igemm.hip", "ada_attention.hip", "ada_elementwise.hip", "ada_pipeline.hip", "ada_eval.hip", "ada_tail.hip", "ada_image.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip", "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip"]
 HEADERS = ["ada_common.h", "ada_igemm_pipe4.inc", os.path.join("..", "..", "include", "ada_hip.h")]
 ARCH = "gfx950"
 # ada_tail.hip: no SLP vectorisation.  Vectorised, the producers' interpolation becomes v_pk_mul_f32 / v_pk_fma_f32 on register pairs
@@ -56,8 +56,10 @@ PER_FILE_FLAGS = {"ada_tail.hip": ["-fno-slp-vectorize"], "ada_igemm.hip": ["-fn
 # ada_raster.hip: a triangle's setup (six snapped coordinates, three w, the area, the box) is a struct of scalars and the pose's 12 doubles arrive in the
 # kernel-argument struct; the resolve's three channels are an array indexed by unrolled constants.  A box is walked with running counters, never an array.
 # ada_adaptive.hip: a triangle is six integer coordinates in scalars, decoded from its heap index by a loop over the path bits; no per-thread array.
+# ada_filters.hip: a thread's window stays in LDS and its rank is selected bit by bit with counters in registers; a window copied into a per-thread array
+# (a sorting network indexed at run time) would live in scratch.
 NO_SCRATCH = {"ada_tail.hip", "ada_igemm.hip", "ada_image.hip", "ada_pipeline.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip",
-              "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip"}
+              "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip"}
 # Round 4: the wrong results above were root-caused (profiles/r04_a_tail_inflight_register_root_cause.txt) -- NOT a hardware hazard of packed
 # fp32 beside MFMAs (tools/ubench/pk_f32_beside_mfma.hip: 0 mismatches) but the compiler copying registers that the kernel's inline-asm
 # fetches were still writing: with SLP on, the allocator parks a source row in other registers with v_mov_b64 placed ABOVE the hand-counted

@@ -831,6 +831,39 @@ def soft_edge(pred, gt, valid, radius, sums, workspace=None):
     _check(load().ada_soft_edge_fwd(pred.data_ptr(), pg, pv, B, h, w, int(radius), ps, ws.data_ptr(), ws_bytes, _stream()), "ada_soft_edge_fwd")
 
 
+def extreme_filter_workspace_bytes(batch: int, h: int, w: int) -> int:
+    """Bytes of workspace ada_extreme_filter_fwd asks for: a key and a one-byte count per pixel."""
+    return 5 * batch * h * w
+
+
+def _filter_maps(who, x, valid, out, count):
+    """(B, h, w, ADA_DT_* of x, pointers of valid / out / count) of a rank filter's maps: x fp32 or uint8 [B, h, w], out of x's type, all of one shape."""
+    if not isinstance(x, torch.Tensor) or x.dtype not in (torch.float32, torch.uint8):
+        raise HipExtError(f"{who}: x must be an fp32 or uint8 tensor, got {getattr(x, 'dtype', type(x).__name__)}")
+    B, h, w = _maps3(who, x, "x", x.dtype)
+    return (B, h, w, DT_F32 if x.dtype == torch.float32 else DT_U8, _like(who, "valid", valid, x, torch.uint8, optional=True),
+            _like(who, "out", out, x, x.dtype), _like(who, "count", count, x, torch.int32, optional=True))
+
+
+def rank_filter_fwd(x, kh, kw, rank, border, out, valid=None, fill=0.0, count=None):
+    """x fp32 / uint8 [B, h, w] -> out: the rank-th order statistic of the valid samples of every kh x kw window (ada_rank_filter_fwd; kh * kw <=
+    FILTER_MAX_WINDOW).  ``rank``: RANK_MIN / RANK_MEDIAN / RANK_MAX or an integer percent 0 .. 100; ``border``: BORDER_*; ``valid``: uint8 [B, h, w] or
+    None; ``fill``: the output where no sample votes; ``count``: optional int32 [B, h, w], the number of voting samples."""
+    who = "rank_filter_fwd"
+    B, h, w, dt, pv, po, pc = _filter_maps(who, x, valid, out, count)
+    _check(load().ada_rank_filter_fwd(x.data_ptr(), pv, dt, B, h, w, int(kh), int(kw), int(rank), int(border), float(fill), po, pc, _stream()), "ada_rank_filter_fwd")
+
+
+def extreme_filter_fwd(x, kh, kw, rank, border, out, valid=None, fill=0.0, count=None, workspace=None):
+    """rank_filter_fwd for RANK_MIN / RANK_MAX on the separable kernels (ada_extreme_filter_fwd; kh, kw <= FILTER_MAX_EXTREME).  ``workspace``: at least
+    extreme_filter_workspace_bytes(B, h, w) bytes, allocated when None."""
+    who = "extreme_filter_fwd"
+    B, h, w, dt, pv, po, pc = _filter_maps(who, x, valid, out, count)
+    ws, ws_bytes = _bytes_of(who, workspace, extreme_filter_workspace_bytes(B, h, w), x.device)
+    _check(load().ada_extreme_filter_fwd(x.data_ptr(), pv, dt, B, h, w, int(kh), int(kw), int(rank), int(border), float(fill), po, pc, ws.data_ptr(), ws_bytes,
+                                         _stream()), "ada_extreme_filter_fwd")
+
+
 # --- tuning / diagnostic hooks (include/ada_hip.h, last section) ---------------------------------
 TILE_NAMES = {0: "256x32", 1: "128x64", 2: "256x128", 3: "256x256", 4: "128x128"}
 

@@ -19,6 +19,7 @@ _CSRC = os.path.join(os.path.dirname(_HERE), "csrc")
 ABI_VERSION = 10
 OK, EINVAL, EUNSUPPORTED, ELAUNCH = 0, -1, -2, -3
 DT_F32, DT_F16, DT_BF16 = 0, 1, 2
+DT_U8 = 3      # x / out of the rank filters
 A_PLAIN, A_CONV3 = 0, 1
 MAP_PLAIN, MAP_PAD, MAP_TOKEN, MAP_SHUFFLE = 0, 1, 2, 3
 EP_BIAS, EP_GELU, EP_GAMMA, EP_RESIDUAL, EP_RELU_OP, EP_SWIGLU, EP_TAIL, EP_RELU_F32 = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40, 0x80
@@ -64,6 +65,13 @@ CANNY_MAX_RADIUS = 16
 SOFT_EDGE_MAX_RADIUS = 8
 EDGE_SUM_BLOCKS = 256
 EDGE_N_BDE, EDGE_SUM_DT, EDGE_N_GT, EDGE_SUM_DP = range(4)
+# ada_rank_filter_fwd / ada_extreme_filter_fwd: border rules, the named ranks (0 .. 100 are integer percents), the window limits, the workgroups' tiles
+BORDER_MIRROR, BORDER_NEAREST, BORDER_IGNORE = 0, 1, 2
+RANK_MIN, RANK_MEDIAN, RANK_MAX = 101, 102, 103
+FILTER_MAX_WINDOW = 81
+FILTER_MAX_EXTREME = 63
+FILTER_TILE_W, FILTER_TILE_H = 64, 4
+FILTER_COL_TILE_H = 16
 
 
 class IgemmArgs(ctypes.Structure):
@@ -166,6 +174,9 @@ PROTOTYPES = {
     "ada_edt_fwd": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
     "ada_edge_metric_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_double, c_void_p, c_void_p, c_int64, c_void_p]),
     "ada_soft_edge_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ada_rank_filter_fwd": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, c_void_p, c_void_p, c_void_p]),
+    "ada_extreme_filter_fwd": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, c_void_p, c_void_p, c_void_p,
+                                       c_int64, c_void_p]),
     "ada_tile_blend_fwd": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "ada_selftest": (c_int, [c_void_p, c_int64, c_void_p]),
     "ada_debug_set_tile": (None, [c_int]),

@@ -268,12 +268,16 @@ def _stage_colors(who, colors, h, w, device):
 
 @torch.no_grad()
 def depth_to_mesh(depth, mask=None, colors=None, compact=True, R=None, t=None, K=None, fov_deg=55.0, inverse=None, max_ratio=None,
-                  dtype=torch.float32, max_error=None, device=None) -> Mesh:
+                  dtype=torch.float32, max_error=None, median=None, device=None) -> Mesh:
     """One depth map fp32 [h, w] -> a Mesh: depth_to_points, then create_triangles over ``mask`` (uint8 / bool [h, w] or None) with the validity and ratio
     rules applied from the same map.  ``colors``: uint8 [h, w, 3] per vertex, or None.  ``compact=True`` keeps only the vertices a triangle uses, in
     raster order, and renumbers the triangles; False keeps all h w points (invalid ones NaN or behind the camera, used by no triangle).
     ``max_error``: None is create_triangles' two triangles per cell; a number takes adaptive_triangles' mesh for that tolerance on the relative disparity
     error instead (h, w >= 2) -- far fewer triangles over flat ground, the same cover, and with compact only the vertices it uses.
+    ``median``: None, or an odd window K (or (kh, kw)) -- the depth inside the mask is first replaced by
+    hip_ext.filters.median_filter(depth, K, border='nearest', valid=mask), the remedy for the flying pixels of an occlusion border, which the ratio
+    rule cuts into holes but which otherwise stand as spikes; only samples inside the mask vote, pixels outside it keep their own value, and points and
+    triangles (regular or adaptive) are built from the filtered map.
     Host reads: the triangle count, and with compact the vertex count."""
     who = "depth_to_mesh"
     h, w, was2d = _check_depth(who, depth)
@@ -284,6 +288,11 @@ def depth_to_mesh(depth, mask=None, colors=None, compact=True, R=None, t=None, K
     device = resolve_device(who, device, depth, mask)
     with torch.cuda.device(device):
         d = _stage_depth(who, depth, device)[0]
+        if median is not None:
+            from .filters import median_filter
+            m = None if mask is None else _stage_mask(who, mask, device)[0]
+            filtered = median_filter(d, median, border="nearest", valid=m, device=device)
+            d = filtered if m is None else torch.where(m != 0, filtered, d)
         col = _stage_colors(who, colors, h, w, device)
         points = depth_to_points(d, R=R, t=t, K=K, fov_deg=fov_deg, inverse=inverse, dtype=dtype, device=device).reshape(1, h * w, 3)
         if max_error is None:
@@ -305,7 +314,7 @@ def depth_to_mesh(depth, mask=None, colors=None, compact=True, R=None, t=None, K
 
 
 @torch.no_grad()
-def amodal_layers(result, image=None, near=1.0, far=10.0, fov_deg=55.0, max_ratio=None, max_error=None) -> Layers:
+def amodal_layers(result, image=None, near=1.0, far=10.0, fov_deg=55.0, max_ratio=None, max_error=None, median=None) -> Layers:
     """The layered geometry of an AmodalResult (hip_ext.pipeline.amodal_infer_image): the scene Mesh from ``result.base`` over every pixel and one Mesh per
     object from ``result.blended[k]`` over ``result.masks[k] > 0`` -- the occluded object reconstructed behind its occluder.
 
@@ -314,7 +323,8 @@ def amodal_layers(result, image=None, near=1.0, far=10.0, fov_deg=55.0, max_rati
     no finite z: it is an invalid vertex and belongs to no triangle.  ``image``: the photo, uint8 [h, w, 3] in B, G, R order, brought to the maps' size by
     hip_ext.image.resize_nearest's rule, gives the vertex colours (stored R, G, B).  An all-zero mask gives an empty Mesh.  base and blended must have one
     size (call amodal_infer_image with the same out_size for both, its default).  ``max_error``: depth_to_mesh's, for every layer -- the error is then
-    measured on the networks' own output, in which the disparity is linear."""
+    measured on the networks' own output, in which the disparity is linear.  ``median``: depth_to_mesh's, for every layer: each object's map is filtered
+    among the samples of its own mask."""
     who = "amodal_layers"
     base, blended, masks = result.base, result.blended, result.masks
     for name, v in (("base", base), ("blended", blended), ("masks", masks)):
@@ -338,7 +348,7 @@ def amodal_layers(result, image=None, near=1.0, far=10.0, fov_deg=55.0, max_rati
                 raise ValueError(f"{who}: image must be uint8 [h, w, 3] in B, G, R order")
             planes = img.to(base.device)[:, :, :3].permute(2, 0, 1).float().contiguous()
             colors = resize_nearest(planes, h, w).flip(0).permute(1, 2, 0).to(torch.uint8).contiguous()      # R, G, B
-        kw = dict(colors=colors, fov_deg=fov_deg, inverse=inverse, max_ratio=max_ratio, max_error=max_error)
+        kw = dict(colors=colors, fov_deg=fov_deg, inverse=inverse, max_ratio=max_ratio, max_error=max_error, median=median)
         scene = depth_to_mesh(base.float(), **kw)
         objects = [depth_to_mesh(blended[k].float(), mask=(masks[k] > 0), **kw) for k in range(blended.shape[0])]
     return Layers(scene, objects)

@@ -2,6 +2,10 @@
 filter of ``remove_small_noise`` (app.py:283-293) and the prompt points of ``get_points_from_components`` (app.py:77-99).  The reference runs
 cv2.connectedComponents / connectedComponentsWithStats on the host; here the mask never leaves HBM (csrc/ada_masks.hip).
 
+Morphology by a square: ``erode`` / ``dilate`` / ``opening`` / ``closing`` (cv2.erode, cv2.dilate, MORPH_OPEN, MORPH_CLOSE with their default border, under
+which the image's outside never decides a pixel) are the separable minimum / maximum of csrc/ada_filters.hip, and ``invisible_mask`` is the chain the
+reference's demo applies to ``whole & ~visible`` (app.py:207-211).
+
 Numbering: components are numbered 1 .. n in the raster order of their first pixels (scipy.ndimage.label's numbering).  OpenCV does not document
 its numbering, so label-for-label equality with cv2 is not claimed; the cleaned mask and the set of points per component do not depend on it.
 
@@ -14,7 +18,8 @@ from collections import namedtuple
 
 import torch
 
-from . import mask_grid_points, mask_keep_area, mask_label, mask_stats
+from . import (BORDER_IGNORE, FILTER_MAX_EXTREME, RANK_MAX, RANK_MIN, extreme_filter_fwd, extreme_filter_workspace_bytes, mask_grid_points,
+               mask_keep_area, mask_label, mask_stats)
 from ._staging import as_int, check_planar, resolve_device, stage_planar
 
 Components = namedtuple("Components", "labels count stats centroids")
@@ -130,3 +135,81 @@ def points_from_components(masks, small_component_thresh=100, grid_step=10, conn
             order = torch.sort(keys, stable=True)[1]                       # by label; the grid points of one component keep their raster order
             out.append(pts[order].to(torch.int32).reshape(-1, 2))
     return out
+
+
+def _square(who, size, iterations):
+    k, it = as_int(size), as_int(iterations)
+    if k is None or k < 1 or k % 2 == 0 or k > FILTER_MAX_EXTREME:
+        raise ValueError(f"{who}: size must be an odd integer in 1 .. {FILTER_MAX_EXTREME}, got {size!r}")
+    if it is None or it < 0:
+        raise ValueError(f"{who}: iterations must be an integer >= 0, got {iterations!r}")
+    return k, it
+
+
+def _morph(who, masks, steps, size, iterations, device):
+    """uint8 0 / 1 [K, h, w] (or [h, w]): the binarised masks after ``iterations`` minimum (RANK_MIN) or maximum (RANK_MAX) filters per entry of ``steps``
+    by a size x size square under BORDER_IGNORE.  The passes ping-pong between two buffers and share one workspace."""
+    k, it = _square(who, size, iterations)
+    single = check_planar(who, masks, (torch.uint8, torch.bool))
+    src, device = _stage(masks, device, who)
+    with torch.cuda.device(device):
+        cur = (src != 0).to(torch.uint8)      # non-zero counts as 1; a fresh packed buffer, the caller's mask is never written
+        nxt = torch.empty_like(cur)
+        ws = torch.empty((extreme_filter_workspace_bytes(*cur.shape) + 7) // 8, dtype=torch.int64, device=device)
+        for rank in steps:
+            for _ in range(it):
+                extreme_filter_fwd(cur, k, k, rank, BORDER_IGNORE, nxt, workspace=ws)
+                cur, nxt = nxt, cur
+    return cur[0] if single else cur
+
+
+@torch.no_grad()
+def erode(masks, size=3, iterations=1, device=None) -> torch.Tensor:
+    """cv2.erode(mask, ones((size, size)), iterations=iterations) with cv2's default border: uint8 0 / 1 on the device, 1 where every pixel of the
+    size x size square that lies inside the image is non-zero (scipy's binary_erosion with border_value=1)."""
+    return _morph("erode", masks, (RANK_MIN,), size, iterations, device)
+
+
+@torch.no_grad()
+def dilate(masks, size=3, iterations=1, device=None) -> torch.Tensor:
+    """cv2.dilate(mask, ones((size, size)), iterations=iterations): uint8 0 / 1 on the device, 1 where any pixel of the square is non-zero (scipy's
+    binary_dilation with border_value=0)."""
+    return _morph("dilate", masks, (RANK_MAX,), size, iterations, device)
+
+
+@torch.no_grad()
+def opening(masks, size=3, iterations=1, device=None) -> torch.Tensor:
+    """cv2.morphologyEx(mask, MORPH_OPEN, ones((size, size)), iterations=iterations): ``iterations`` erosions, then as many dilations.  Not scipy's
+    binary_opening, whose erosion takes the image's outside as 0."""
+    return _morph("opening", masks, (RANK_MIN, RANK_MAX), size, iterations, device)
+
+
+@torch.no_grad()
+def closing(masks, size=3, iterations=1, device=None) -> torch.Tensor:
+    """cv2.morphologyEx(mask, MORPH_CLOSE, ones((size, size)), iterations=iterations): ``iterations`` dilations, then as many erosions -- pinholes and
+    hairline gaps narrower than the square close.  Not scipy's binary_closing, whose erosion takes the image's outside as 0."""
+    return _morph("closing", masks, (RANK_MAX, RANK_MIN), size, iterations, device)
+
+
+@torch.no_grad()
+def invisible_mask(visible, whole, min_area=None, erode=None, close=None, connectivity=4) -> torch.Tensor:
+    """The occluded part of an object: ``whole & ~visible`` (the dataset's definition, sam_amodal_dataset.py:42), uint8 0 / 1 on the device, then the
+    clean-up chain of the reference's demo (app.py:207-211) in its order: remove_small_noise(min_area, connectivity), erosion by an ``erode`` square,
+    closing by a ``close`` square.  A step whose argument is None does not run.  visible, whole: masks of one shape, non-zero = set."""
+    who = "invisible_mask"
+    single = check_planar(who, whole, (torch.uint8, torch.bool))
+    check_planar(who, visible, (torch.uint8, torch.bool))
+    if tuple(visible.shape) != tuple(whole.shape):
+        raise ValueError(f"{who}: visible {tuple(visible.shape)} and whole {tuple(whole.shape)} differ in shape")
+    connectivity = _connectivity(who, connectivity)
+    wh, device = _stage(whole, None, who)
+    vis, _ = _stage(visible, device, who)
+    with torch.cuda.device(device):
+        out = ((wh != 0) & (vis == 0)).to(torch.uint8)
+    if min_area is not None:
+        out = remove_small_noise(out, min_area=min_area, connectivity=connectivity, device=device)
+    if erode is not None:
+        out = _morph(who, out, (RANK_MIN,), erode, 1, device)      # the argument shadows erode()
+    if close is not None:
+        out = _morph(who, out, (RANK_MAX, RANK_MIN), close, 1, device)
+    return out[0] if single else out

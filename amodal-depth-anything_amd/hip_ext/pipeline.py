@@ -76,7 +76,7 @@ def fit_scale_shift(amodal: torch.Tensor, base: torch.Tensor, visible: torch.Ten
 
 @torch.no_grad()
 def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None, size: int = 518, out_size=None, check: bool = True,
-                       render: bool = False, min_area=None, min_area_connectivity: int = 4, render_percentiles=None):
+                       render: bool = False, min_area=None, min_area_connectivity: int = 4, render_percentiles=None, close=None):
     """The reference's infer.py call on the device: a decoded uint8 BGR(A) photo [h, w, 3 | 4] and K amodal masks (uint8 / bool [h, w] or
     [K, h, w]) in, an AmodalResult out.  The base network runs once (B = 1), the amodal network once as a batch of K.
 
@@ -92,7 +92,10 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
     filter, app.py:283-293: components of fewer than min_area pixels under min_area_connectivity go) -- specks of a segmenter's mask would otherwise be
     guidance for the network and receive pasted depth.  The visible masks are not touched.  None: nothing runs, the call is exactly the one without it.
     render_percentiles: (lo, hi) in [0, 100] -- with render=True each picture is coloured between these percentiles of its own map (colorize()'s range,
-    hip_ext.quantile.percentile_range, taken on the device) instead of between 0 and 1.  None: the pictures are exactly the ones without it."""
+    hip_ext.quantile.percentile_range, taken on the device) instead of between 0 and 1.  None: the pictures are exactly the ones without it.
+    close: when given, the AMODAL masks are closed by a close x close square (hip_ext.masks.closing, the MORPH_CLOSE of app.py:211), at their own
+    resolution, after the min_area step -- a segmenter's pinholes and hairline gaps would otherwise be guidance for the network and keep the base depth
+    in the paste.  None: nothing runs, the call is exactly the one without it."""
     from ._staging import as_int
     from .image import _check_size, masks_to_tensor, photo_to_inputs, render_depth, resize_nearest
     size = _check_size(size, "amodal_infer_image")
@@ -104,6 +107,9 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
     if min_area is not None:
         from .masks import remove_small_noise
         masks = remove_small_noise(masks, min_area=min_area, connectivity=min_area_connectivity, device=device)
+    if close is not None:
+        from .masks import closing
+        masks = closing(masks, size=close, device=device)
     mask01, guide = masks_to_tensor(masks, size, device, guide=True)
     K, S = mask01.shape[0], size
     visible = None

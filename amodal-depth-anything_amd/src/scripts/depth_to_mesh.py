@@ -2,7 +2,7 @@
 """A depth map in, a triangle mesh out: the reference's ``zoedepth/utils/geometry.py`` (depth_to_points, create_triangles) as a command line.
 
     python -m src.scripts.depth_to_mesh DEPTH OUTPUT.ply [--mask MASK.png] [--inverse NEAR FAR] [--max_ratio R] [--fov 55] [--image PHOTO]
-                                                        [--max_error E]
+                                                        [--max_error E] [--median K]
 
 DEPTH is a 16-bit (or 8-bit) one-channel PNG / TIFF read with Pillow, or a ``.npy`` float array.  Without ``--inverse`` its values are depths, as the
 reference takes them.  With ``--inverse NEAR FAR`` they are normalised inverse depth -- what this project's networks and its 16-bit pseudo-labels hold:
@@ -10,7 +10,9 @@ an integer image is first divided by its type's largest value, and v in [0, 1] b
 the triangle selection (inside MASK, valid depth, and with ``--max_ratio`` no triangle whose farthest vertex is more than R times its nearest) and the
 vertex compaction run on the device (hip_ext.geometry); the PLY is written on the host.  ``--max_error E`` writes an adaptive mesh in place of two
 triangles per pixel cell: conforming right triangles refined until the relative disparity error at every split point is at most E
-(hip_ext.geometry.adaptive_triangles) -- 0.01 keeps a few per cent of the triangles of a smooth map.
+(hip_ext.geometry.adaptive_triangles) -- 0.01 keeps a few per cent of the triangles of a smooth map.  ``--median K`` first replaces the depth inside
+the mask by its K x K median among the mask's own samples (hip_ext.filters.median_filter, on the device): the flying pixels of an occlusion border
+otherwise stand as spikes.
 """
 import argparse
 import os
@@ -48,7 +50,7 @@ def read_mask(path, shape) -> np.ndarray:
     return np.ascontiguousarray((m > 0).astype(np.uint8))
 
 
-def mesh_file(src, dst, mask=None, inverse=None, max_ratio=None, fov=55.0, image=None, device="cuda", max_error=None):
+def mesh_file(src, dst, mask=None, inverse=None, max_ratio=None, fov=55.0, image=None, device="cuda", max_error=None, median=None):
     """Meshes one file; returns the hip_ext.geometry.Mesh that was written."""
     depth = read_depth(src, normalise=inverse is not None)
     ab = None
@@ -63,7 +65,7 @@ def mesh_file(src, dst, mask=None, inverse=None, max_ratio=None, fov=55.0, image
         if colors.shape[:2] != depth.shape:
             raise ValueError(f"{image}: photo of shape {colors.shape[:2]} for a depth map of shape {depth.shape}")
     mesh = geometry.depth_to_mesh(depth, mask=None if mask is None else read_mask(mask, depth.shape), colors=colors, fov_deg=fov, inverse=ab,
-                                  max_ratio=max_ratio, max_error=max_error, device=device)
+                                  max_ratio=max_ratio, max_error=max_error, median=median, device=device)
     os.makedirs(os.path.dirname(os.path.abspath(dst)), exist_ok=True)
     geometry.write_ply(dst, mesh)
     return mesh
@@ -79,9 +81,10 @@ def main(argv=None):
     ap.add_argument("--fov", type=float, default=55.0, help="field of view of the pinhole camera in degrees")
     ap.add_argument("--image", default=None, help="a photo of the depth map's size for the vertex colours")
     ap.add_argument("--max_error", type=float, default=None, help="adaptive mesh: the largest relative disparity error of a triangle that is not split (default: two triangles per cell)")
+    ap.add_argument("--median", type=int, default=None, metavar="K", help="median-filter the depth over K x K windows (K odd) among the samples inside the mask before meshing: removes the flying pixels of occlusion borders")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
-    mesh = mesh_file(args.input, args.output, args.mask, args.inverse, args.max_ratio, args.fov, args.image, args.device, args.max_error)
+    mesh = mesh_file(args.input, args.output, args.mask, args.inverse, args.max_ratio, args.fov, args.image, args.device, args.max_error, args.median)
     print(f"{args.output}: {mesh.vertex_count} vertices, {mesh.triangle_count} triangles")
     return 0
 

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ADA_ABI_VERSION 10   /* 10: + ada_photo_prep_fwd, ada_mask_prep_fwd, ada_nearest_resize_fwd, ada_blend_ex (the amodal infer_image; exports only, no signature changed); later, still 10: + ada_depth_render_fwd (the rendering of infer.py:106-119; one more export, no signature changed, so a caller built against the earlier 10 runs unchanged).  History: 9: + ada_image_prep_fwd, ada_depth_resize_fwd (the raw model's infer_image; exports only, no signature changed).  History: 8 (round 6): the default-off experiment paths that lost are gone -- ada_igemm_args without ln_stats / ln_colsum / rowstat_out (EP_LNFOLD / EP_ROWSTATS) and the LayerNorm tail (ln_*), no ada_rowstats_finalize.  History: 6 (round 5): + ada_depth_stats_fwd, ada_token_diversity_fwd; 7: ada_igemm_args grows f8_from / f8_mid / f8_scales at its end and split_seg < 0 names the fp8 form of a split output (a zero-filled tail = off: every ABI-6 call means what it meant) */
+#define ADA_ABI_VERSION 10   /* still 10: + ada_rank_filter_fwd, ada_extreme_filter_fwd (the rank filters; two more exports, no signature changed, so a caller built against the earlier 10 runs unchanged).  10: + ada_photo_prep_fwd, ada_mask_prep_fwd, ada_nearest_resize_fwd, ada_blend_ex (the amodal infer_image; exports only, no signature changed); later, still 10: + ada_depth_render_fwd (the rendering of infer.py:106-119; one more export, no signature changed, so a caller built against the earlier 10 runs unchanged).  History: 9: + ada_image_prep_fwd, ada_depth_resize_fwd (the raw model's infer_image; exports only, no signature changed).  History: 8 (round 6): the default-off experiment paths that lost are gone -- ada_igemm_args without ln_stats / ln_colsum / rowstat_out (EP_LNFOLD / EP_ROWSTATS) and the LayerNorm tail (ln_*), no ada_rowstats_finalize.  History: 6 (round 5): + ada_depth_stats_fwd, ada_token_diversity_fwd; 7: ada_igemm_args grows f8_from / f8_mid / f8_scales at its end and split_seg < 0 names the fp8 form of a split output (a zero-filled tail = off: every ABI-6 call means what it meant) */
 
 /* status codes */
 #define ADA_OK 0
@@ -881,6 +881,57 @@ int ada_edge_metric_fwd(const uint8_t* pred_edges, const uint8_t* gt_edges, cons
                         int32_t batch, int32_t h, int32_t w, double th_acc, double* sums, void* workspace, int64_t workspace_bytes, void* stream);
 int ada_soft_edge_fwd(const float* pred, const float* gt, const uint8_t* valid, int32_t batch, int32_t h, int32_t w, int32_t radius, double* sums,
                       void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Rank filters: the windowed order statistic of the VALID samples (additions under ABI 10).  Median, minimum (erosion) and maximum (dilation) are ranks of it;
+ * opening and closing are compositions (hip_ext/masks.py).  The reference has no such operation on the device or off it: its median_filter_blend
+ * (app.py:267, infer.py:30) runs cv2.blur, and its mask clean-up (app.py:207-211: cv2.erode, MORPH_CLOSE) runs on the host.
+ *   INPUT.  x: fp32 (dtype ADA_DT_F32) or uint8 (ADA_DT_U8), packed [batch][h][w].  valid: optional uint8 of that shape, non-zero = the sample
+ *     votes (NULL: every sample).  The window is kh x kw, both odd, radii rh = kh / 2 and rw = kw / 2.  h * w < 2^31, batch <= 65535, h and w down to 1.
+ *   SAMPLES of output pixel (y, x): the positions (y + dy, x + dx), |dy| <= rh, |dx| <= rw, each axis mapped by the border rule
+ *     ADA_BORDER_MIRROR   reflect-101: period 2 n - 2, the index reduced modulo the period, so a window wider than the image is legal; n == 1: index 0
+ *                         (scipy's 'mirror', cv2's BORDER_REFLECT_101)
+ *     ADA_BORDER_NEAREST  clamped into the image (scipy's 'nearest', cv2's BORDER_REPLICATE)
+ *     ADA_BORDER_IGNORE   positions outside the image are dropped
+ *     A mapped position contributes when valid is absent or non-zero there and, for fp32, the value is not NaN.  Mirrored or clamped duplicates count
+ *     once each: the samples are a multiset of n values.
+ *   RESULT.  n == 0: out = fill (converted to x's type; for uint8 an integer in 0 .. 255) and count = 0.  Otherwise the samples sorted ascending by IEEE
+ *     comparison (+-inf order as numbers; -0 and +0 are equal and either may come out), s[0 .. n - 1], and out = s[r] with
+ *     ADA_RANK_MIN     r = 0
+ *     ADA_RANK_MAX     r = n - 1
+ *     ADA_RANK_MEDIAN  r = n / 2              scipy's upper median: scipy.ndimage.median_filter when every sample votes
+ *     0 <= rank <= 100 r = rank (n - 1) / 100 an integer percent; the quotient in integers, rounded down
+ *     out is always one of the input values: no arithmetic touches a value.  count: optional int32 [batch][h][w] (NULL: not written), receives n.
+ *   ada_rank_filter_fwd      any rank; kh * kw <= ADA_FILTER_MAX_WINDOW (9 x 9, 3 x 27, ...), else ADA_EINVAL before any launch.  One workgroup
+ *     per tile of ADA_FILTER_TILE_H x ADA_FILTER_TILE_W outputs stages tile and halo into LDS once, as order-preserving 32-bit keys (an fp32's bits
+ *     with the sign bit flipped, all bits flipped when negative; a uint8 as it is) with one key value marking invalid, NaN and dropped samples.
+ *     Each thread then selects s[r] bit by bit, from the top: a bit stays set when at most r keys of the window lie below the candidate -- 32 passes
+ *     (8 for uint8) over the window in LDS, no per-thread array, trip counts that depend on (kh, kw) alone.
+ *   ada_extreme_filter_fwd   rank ADA_RANK_MIN or ADA_RANK_MAX only; kh, kw <= ADA_FILTER_MAX_EXTREME, else ADA_EINVAL before any launch.
+ *     Separable: a row pass (tiles of ADA_FILTER_TILE_H x ADA_FILTER_TILE_W) writes per pixel the extreme key and the number of valid samples of its
+ *     kw row neighbours, a column pass (tiles of ADA_FILTER_COL_TILE_H x ADA_FILTER_TILE_W) combines kh of them.  An invalid sample contributes the
+ *     identity element; the extreme of extremes and the integer sum of counts are exact, so the result equals ada_rank_filter_fwd's.
+ *     workspace  workspace_bytes >= 5 batch h w (a key and a one-byte count per pixel), 4-byte aligned  (checked)
+ *   Both read nothing back, allocate nothing, use no atomics and launch one fixed grid derived from the shapes: legal inside a stream capture, the
+ *   same bytes every run.  Offsets into the maps are 64-bit.
+ * ---------------------------------------------------------------------------------------- */
+#define ADA_DT_U8 3                    /* x / out of the rank filters: uint8 */
+#define ADA_BORDER_MIRROR 0
+#define ADA_BORDER_NEAREST 1
+#define ADA_BORDER_IGNORE 2
+#define ADA_RANK_MIN 101               /* ranks 0 .. 100 are integer percents */
+#define ADA_RANK_MEDIAN 102
+#define ADA_RANK_MAX 103
+#define ADA_FILTER_MAX_WINDOW 81       /* kh * kw of ada_rank_filter_fwd */
+#define ADA_FILTER_MAX_EXTREME 63      /* kh and kw of ada_extreme_filter_fwd */
+#define ADA_FILTER_TILE_W 64           /* outputs per workgroup: ADA_FILTER_TILE_H rows of ADA_FILTER_TILE_W */
+#define ADA_FILTER_TILE_H 4
+#define ADA_FILTER_COL_TILE_H 16       /* rows per workgroup of the extremes' column pass */
+int ada_rank_filter_fwd(const void* x, const uint8_t* valid, int32_t dtype, int32_t batch, int32_t h, int32_t w, int32_t kh, int32_t kw,
+                        int32_t rank, int32_t border, double fill, void* out, int32_t* count, void* stream);
+int ada_extreme_filter_fwd(const void* x, const uint8_t* valid, int32_t dtype, int32_t batch, int32_t h, int32_t w, int32_t kh, int32_t kw,
+                           int32_t rank, int32_t border, double fill, void* out, int32_t* count, void* workspace, int64_t workspace_bytes,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Tiled inference for inputs larger than the network's native 518 x 518 (the reference squashes every
