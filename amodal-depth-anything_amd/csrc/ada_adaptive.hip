@@ -13,18 +13,21 @@
 // index.  The tree is cut at the level whose cells are ADA_ADAPT_CELL wide: above it one workgroup walks the levels breadth first, keeping only
 // triangles whose bounding box overlaps the image -- the lists stay in heap order and their sizes depend on the shapes alone; at the cut these are
 // the two halves of every cell that overlaps the image, 2 ceil((h - 1) / cell) ceil((w - 1) / cell) subtrees.  Below it one workgroup per subtree
-// decodes its triangles from the path bits.  Counts per (level, subtree) in heap order, one scan, then the subtrees' walk again writes the rows (the
-// levels above the cut come first in heap order: their workgroup writes its rows while it counts).
+// decodes its triangles from the path bits.  Counts per (level, subtree) in heap order, one scan (scan_sums_kernel<8> of ada_scan.h, whose block
+// prefixes also place the rows), then the subtrees' walk again writes the rows (the levels above the cut come first in heap order: their workgroup
+// writes its rows while it counts).  The depth -> z rule of a keepable leaf is ada_mesh_rule.h's, shared with ada_geometry.hip.
 // No subtree wholly outside the image is launched over or descended into, no atomic decides a position: the same bytes every run.
 //
 // Every launch sequence is fixed by the shapes and the flags; nothing is read back and nothing allocated: legal inside a stream capture.
-#include "ada_common.h"
+#include "ada_mesh_rule.h"
+#include "ada_scan.h"
 
 namespace {
 
-constexpr int AD_WAVE = 64;
+constexpr int AD_WAVE = ADA_WAVE;
 constexpr int AD_THREADS = 256;                      // the per-level error launches and the per-subtree walks
-constexpr int AD_TOP = 1024;                         // the one workgroup of the folded levels, of the breadth-first walk and of the scan
+constexpr int AD_TOP = 1024;                         // the one workgroup of the folded levels and of the breadth-first walk
+constexpr int AD_SCAN_ITEMS = 8;                     // sums per thread and step of the scan: the 6 400 sums of a 518 x 518 map take one step
 constexpr int AD_FOLD = ADA_ADAPT_FOLD;
 constexpr int AD_CELL = ADA_ADAPT_CELL;
 constexpr int AD_MAX_N = ADA_ADAPT_MAX_N;
@@ -38,8 +41,7 @@ struct AdArgs {
     const uint8_t* mask;     // or NULL: every vertex inside
     long mask_pitch;
     const float* depth;      // [h][w]
-    int inverse;             // 0: z = depth, omega = 1 / depth; 1: omega = a depth + b, z = 1 / omega
-    double a, b;
+    ZRule z;                 // and omega = 1 / z: omega_of
     double max_ratio;        // <= 0: off
     int h, w, N, levels;     // levels = 2 log2 N + 1
     double* E;               // [h][w]
@@ -56,23 +58,17 @@ struct AdArgs {
 
 ADA_DEV double d_inf() { return __builtin_inf(); }
 
-ADA_DEV double z_of(const AdArgs& p, float d) {
-    const double v = (double)d;
-    if (!p.inverse) return v;
-    return 1.0 / __dadd_rn(__dmul_rn(p.a, v), p.b);
-}
 ADA_DEV double omega_of(const AdArgs& p, int i, int j) {
     const double v = (double)p.depth[i * p.w + j];
-    if (!p.inverse) return 1.0 / v;
-    return __dadd_rn(__dmul_rn(p.a, v), p.b);
+    if (!p.z.inverse) return 1.0 / v;
+    return __dadd_rn(__dmul_rn(p.z.a, v), p.z.b);
 }
-ADA_DEV bool z_valid(double z) { return z > 0.0 && z < __builtin_inf(); }
 
 // present, inside the mask and valid: the three per-vertex tests of create_triangles; z is set when it returns true
 ADA_DEV bool vertex_ok(const AdArgs& p, int i, int j, double& z) {
     if ((unsigned)i >= (unsigned)p.h || (unsigned)j >= (unsigned)p.w) return false;
     if (p.mask && p.mask[(long)i * p.mask_pitch + j] == 0) return false;
-    z = z_of(p, p.depth[i * p.w + j]);
+    z = z_of(p.z, p.depth[i * p.w + j]);
     return z_valid(z);
 }
 
@@ -159,50 +155,6 @@ __global__ __launch_bounds__(AD_TOP) void err_fold_kernel(AdArgs p, int l_start)
 }
 
 // ------------------------------------------------------------------ emission
-// exclusive prefix of v over the workgroup's threads in order, and the workgroup's total
-template <int THREADS>
-ADA_DEV int block_excl(int v, int* lds, int& total) {
-    const int lane = threadIdx.x & (AD_WAVE - 1), wave = threadIdx.x / AD_WAVE;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < AD_WAVE; d <<= 1) {
-        const int o = __shfl_up(incl, d, AD_WAVE);
-        if (lane >= d) incl += o;
-    }
-    __syncthreads();      // the previous round's readers are done
-    if (lane == AD_WAVE - 1) lds[wave] = incl;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < THREADS / AD_WAVE; ++k) {
-        const int t = lds[k];
-        before += k < wave ? t : 0;
-        total += t;
-    }
-    return before + incl - v;
-}
-
-// exclusive prefix of a flag over the workgroup's threads in order: one ballot per wave, the waves' totals through LDS
-template <int THREADS>
-ADA_DEV int block_excl_flag(bool f, int* lds, int& total) {
-    const uint64_t bal = __ballot(f);
-    const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-    const int wave = threadIdx.x / AD_WAVE;
-    __syncthreads();      // the previous round's readers are done
-    if ((threadIdx.x & (AD_WAVE - 1)) == 0) lds[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < THREADS / AD_WAVE; ++k) {
-        const int t = lds[k];
-        before += k < wave ? t : 0;
-        total += t;
-    }
-    return before + below;
-}
-
 // THE predicate: is the triangle (a, b, c) of level l a row of the output
 ADA_DEV bool emit(const AdArgs& p, int l, int ai, int aj, int bi, int bj, int ci, int cj) {
     // c is the parent's hypotenuse midpoint: the parent was split when E[c] > tau (an absent c: +inf)
@@ -254,7 +206,7 @@ __global__ __launch_bounds__(AD_TOP) void top_kernel(AdArgs p) {
             const bool f1 = have && overlaps(p, n.bi, n.bj, n.ci, n.cj, mi, mj);      // right child (b, c, m)
             // children in the low 16 bits (at most 2 AD_TOP a step), rows above them (at most AD_TOP)
             int total;
-            const int before = block_excl<AD_TOP>((f0 ? 1 : 0) + (f1 ? 1 : 0) + (e ? 1 << 16 : 0), lds, total);
+            const int before = block_excl<AD_TOP / AD_WAVE>((f0 ? 1 : 0) + (f1 ? 1 : 0) + (e ? 1 << 16 : 0), lds, total);
             int pos = n_next + (before & 0xFFFF);
             if (f0 && pos < p.list_cap) { Node c = {2 * n.t, n.ci, n.cj, n.ai, n.aj, mi, mj, 0}; nxt[pos] = c; }
             pos += f0 ? 1 : 0;
@@ -308,7 +260,7 @@ __global__ __launch_bounds__(AD_THREADS) void sub_kernel(AdArgs p) {
             const bool e = have && emit(p, l, ai, aj, bi, bj, ci, cj);
             if (SCATTER) {
                 int total_e;
-                const int pe = block_excl_flag<AD_THREADS>(e, lds, total_e);
+                const int pe = block_excl_flag<AD_THREADS / AD_WAVE>(e, lds, total_e);
                 if (e) write_row(p, out0 + emitted + pe, ai, aj, bi, bj, ci, cj);
                 emitted += total_e;
             } else {
@@ -321,32 +273,6 @@ __global__ __launch_bounds__(AD_THREADS) void sub_kernel(AdArgs p) {
         __syncthreads();
         if ((int)threadIdx.x <= depth) p.sums[(long)p.lb + (long)threadIdx.x * p.n_sub + r] = lds[threadIdx.x];
     }
-}
-
-// sums[0 .. n) -> exclusive prefix sums in place, *total = their sum.  One workgroup, AD_SCAN_ITEMS consecutive sums per thread and step.
-constexpr int AD_SCAN_ITEMS = 8;
-__global__ __launch_bounds__(AD_TOP) void scan_kernel(int32_t* s, long n, int32_t* total) {
-    __shared__ int lds[AD_TOP / AD_WAVE];
-    int carry = 0;
-    for (long base = 0; base < n; base += (long)AD_TOP * AD_SCAN_ITEMS) {
-        const long i0 = base + (long)threadIdx.x * AD_SCAN_ITEMS;
-        int v[AD_SCAN_ITEMS];
-        int mine = 0;
-#pragma unroll
-        for (int k = 0; k < AD_SCAN_ITEMS; ++k) {
-            v[k] = i0 + k < n ? s[i0 + k] : 0;
-            mine += v[k];
-        }
-        int all;
-        int run = carry + block_excl<AD_TOP>(mine, lds, all);
-#pragma unroll
-        for (int k = 0; k < AD_SCAN_ITEMS; ++k) {
-            if (i0 + k < n) s[i0 + k] = run;
-            run += v[k];
-        }
-        carry += all;
-    }
-    if (threadIdx.x == 0) *total = carry;
 }
 
 struct Plan {
@@ -396,14 +322,11 @@ extern "C" int ada_mesh_adaptive_fwd(const uint8_t* mask, int64_t row_pitch_byte
     ADA_REQUIRE(batch >= 1 && batch <= 65535 && adapt_shape_ok(h, w), ADA_EINVAL,
                 "ada_mesh_adaptive_fwd: batch=%d h=%d w=%d outside 1..65535 / h, w >= 2 / h * w < 2^30", batch, h, w);
     ADA_REQUIRE((h > w ? h : w) - 1 <= AD_MAX_N, ADA_EUNSUPPORTED, "ada_mesh_adaptive_fwd: h=%d w=%d beyond %d + 1 on a side", h, w, AD_MAX_N);
-    ADA_REQUIRE(capacity >= 0 && (int64_t)batch * capacity * 3 < ((int64_t)1 << 40), ADA_EINVAL, "ada_mesh_adaptive_fwd: capacity=%d", capacity);
-    ADA_REQUIRE(inverse == 0 || inverse == 1, ADA_EINVAL, "ada_mesh_adaptive_fwd: inverse=%d (0 or 1)", inverse);
+    const int rc = mesh_rule_check("ada_mesh_adaptive_fwd", mask, row_pitch_bytes, image_stride_bytes, inverse, max_ratio, batch, h, w, capacity);
+    if (rc != ADA_OK) return rc;
     ADA_REQUIRE(no_max_error == 0 || no_max_error == 1, ADA_EINVAL, "ada_mesh_adaptive_fwd: no_max_error=%d (0 or 1)", no_max_error);
     ADA_REQUIRE(no_max_error || (max_error >= 0.0 && max_error < __builtin_inf()), ADA_EINVAL,
                 "ada_mesh_adaptive_fwd: max_error=%g must be finite and >= 0", max_error);
-    ADA_REQUIRE(!mask || (row_pitch_bytes >= w && (batch == 1 || image_stride_bytes >= (int64_t)(h - 1) * row_pitch_bytes + w)), ADA_EINVAL,
-                "ada_mesh_adaptive_fwd: mask pitch %ld / stride %ld too small for %d x %d", (long)row_pitch_bytes, (long)image_stride_bytes, h, w);
-    ADA_REQUIRE(max_ratio == max_ratio, ADA_EINVAL, "ada_mesh_adaptive_fwd: max_ratio is NaN");
     ADA_REQUIRE(error_ready == 0 || (error_ready == 1 && error_out), ADA_EINVAL, "ada_mesh_adaptive_fwd: error_ready=%d (0, or 1 with error_out)", error_ready);
     const Plan q = make_plan(h, w);
     ADA_REQUIRE(workspace_bytes >= q.bytes && (uintptr_t)workspace % 16 == 0 && (uintptr_t)error_out % 8 == 0, ADA_EINVAL,
@@ -414,7 +337,7 @@ extern "C" int ada_mesh_adaptive_fwd(const uint8_t* mask, int64_t row_pitch_byte
     for (int32_t img = 0; img < batch; ++img) {      // one image after the other on the stream: they share the workspace
         AdArgs p;
         p.mask = mask ? mask + (int64_t)img * image_stride_bytes : nullptr; p.mask_pitch = (long)row_pitch_bytes;
-        p.depth = depth + (int64_t)img * h * w; p.inverse = inverse; p.a = a; p.b = b; p.max_ratio = max_ratio;
+        p.depth = depth + (int64_t)img * h * w; p.z.inverse = inverse; p.z.a = a; p.z.b = b; p.max_ratio = max_ratio;
         p.h = h; p.w = w; p.N = q.N; p.levels = q.levels;
         p.E = error_out ? error_out + (int64_t)img * h * w : (double*)ws;
         p.tau = no_max_error ? 0.0 : max_error; p.none = no_max_error;
@@ -434,7 +357,7 @@ extern "C" int ada_mesh_adaptive_fwd(const uint8_t* mask, int64_t row_pitch_byte
         }
         hipLaunchKernelGGL(top_kernel, dim3(1), dim3(AD_TOP), 0, s, p);
         hipLaunchKernelGGL(sub_kernel<false>, dim3((unsigned)q.n_sub), dim3(AD_THREADS), 0, s, p);
-        hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(AD_TOP), 0, s, p.sums, (long)q.n_sums, count + img);
+        hipLaunchKernelGGL(scan_sums_kernel<AD_SCAN_ITEMS>, dim3(1), dim3(SCAN_THREADS), 0, s, p.sums, (long)q.n_sums, (long)q.n_sums, count + img);
         if (capacity > 0) {
             hipLaunchKernelGGL(sub_kernel<true>, dim3((unsigned)q.n_sub), dim3(AD_THREADS), 0, s, p);
         }

@@ -7,17 +7,19 @@
 // span (a lane's own three coordinates are 12 or 24 bytes, which no store instruction covers without splitting lines between lanes).
 //
 // Triangles.  The candidates are two per pixel cell in raster order; a kept one is a predicate of its three vertices (tri_flags, ONE function used
-// by the counting and the writing pass).  Order-preserving compaction in three launches, none waiting on another workgroup:
-//   count    a workgroup owns GEOM_CHUNK consecutive cells; per 64 candidates one ballot and popcount; its sum goes to sums[image][workgroup]
-//   scan     one workgroup per image turns the sums into exclusive offsets in place and writes the total to count[image]
-//   scatter  the count pass again, each lane's position = offset + kept candidates before it (ballot prefix); rows at or beyond `capacity` are dropped
-// No atomic decides a position: the output is the same bytes every run.
+// by the counting and the writing pass; the depth -> z rule is ada_mesh_rule.h's).  Order-preserving compaction with the pieces of ada_scan.h, in three
+// launches, none waiting on another workgroup:
+//   count    a workgroup owns GEOM_CHUNK consecutive cells and sums their kept candidates into sums[image][workgroup]
+//   scan     scan_sums_kernel<1>, one workgroup per image: exclusive offsets in place, the total to count[image]
+//   scatter  the count pass again: a round of 256 cells takes two ballots per lane (a cell's first and second triangle) and waves_before; a lane's
+//            position = offset + the rounds before + the waves before + the lanes below; rows at or beyond `capacity` are dropped
 //
 // Compaction of the vertices: clear, mark (every referenced vertex gets a 1: a plain store of one value, order-free), the same count / scan over chunks of
-// vertices, gather (new index = offset + marked vertices before it; the point and the colour move there) and remap of the triangle indices in place.
+// vertices, gather (new index = offset + block_excl_flag of the marks; the point and the colour move there) and remap of the triangle indices in place.
 //
 // Every launch sequence is fixed by the shapes alone; nothing is read back: all three calls are legal inside a stream capture.
-#include "ada_common.h"
+#include "ada_mesh_rule.h"
+#include "ada_scan.h"
 
 namespace {
 
@@ -25,21 +27,9 @@ constexpr int GEOM_WAVE = ADA_GEOM_WAVE;
 constexpr int GEOM_THREADS = 256;
 constexpr int GEOM_CHUNK = ADA_GEOM_CHUNK;             // cells (or vertices) per workgroup of the count / scatter passes
 constexpr int GEOM_SUB = GEOM_CHUNK / GEOM_THREADS;    // a thread's cells: t, t + 256, ...
-constexpr int GEOM_SCAN = ADA_GEOM_SCAN_BLOCK;         // workgroup sums per step of the scan
 constexpr int GEOM_WAVES = GEOM_THREADS / GEOM_WAVE;
-static_assert(GEOM_WAVE == 64 && GEOM_CHUNK % GEOM_THREADS == 0 && GEOM_SCAN == 1024, "layout");
-
-struct ZRule {
-    int inverse;     // 0: z = depth; 1: z = 1 / (a * depth + b)
-    double a, b;
-};
-
-ADA_DEV double z_of(const ZRule& r, float d) {
-    const double v = (double)d;
-    if (!r.inverse) return v;
-    return 1.0 / __dadd_rn(__dmul_rn(r.a, v), r.b);     // the correctly rounded quotient: no fast-math flag in this build
-}
-ADA_DEV bool z_valid(double z) { return z > 0.0 && z < __builtin_inf(); }     // finite and positive; false for NaN
+// the published step of the scan is scan_sums_kernel<1>'s: one sum per thread
+static_assert(GEOM_WAVE == ADA_WAVE && GEOM_CHUNK % GEOM_THREADS == 0 && ADA_GEOM_SCAN_BLOCK == SCAN_THREADS * 1, "layout");
 
 // ------------------------------------------------------------------ points
 struct PointArgs {
@@ -113,60 +103,6 @@ __global__ __launch_bounds__(GEOM_THREADS) void points_kernel(PointArgs a) {
     }
 }
 
-// ------------------------------------------------------------------ order-preserving compaction: shared pieces
-// kept items of the lanes below this one, for a per-lane flag
-ADA_DEV int lanes_below(uint64_t ballot) {
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-}
-
-// the workgroup's waves exchange their totals: returns the items of the waves before this one, and the workgroup's total in `total`
-ADA_DEV int waves_before(int* lds, int wave_total, int& total) {
-    const int wave = threadIdx.x / GEOM_WAVE;
-    __syncthreads();                                     // the previous round's readers are done
-    if ((threadIdx.x & (GEOM_WAVE - 1)) == 0) lds[wave] = wave_total;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int i = 0; i < GEOM_WAVES; ++i) {
-        const int v = lds[i];
-        before += i < wave ? v : 0;
-        total += v;
-    }
-    return before;
-}
-
-// sums[image][0 .. n) -> exclusive prefix sums in place, total[image] = their sum.  One workgroup per image, GEOM_SCAN sums per step.
-__global__ __launch_bounds__(GEOM_SCAN) void scan_kernel(int32_t* sums, int n, long stride, int32_t* total) {
-    __shared__ int wsum[GEOM_SCAN / GEOM_WAVE];
-    int32_t* s = sums + (long)blockIdx.x * stride;
-    const int lane = threadIdx.x & (GEOM_WAVE - 1), wave = threadIdx.x / GEOM_WAVE;
-    int carry = 0;
-    for (int base = 0; base < n; base += GEOM_SCAN) {
-        const int i = base + threadIdx.x;
-        const int v = i < n ? s[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int d = 1; d < GEOM_WAVE; d <<= 1) {
-            const int o = __shfl_up(incl, d, GEOM_WAVE);
-            if (lane >= d) incl += o;
-        }
-        if (lane == GEOM_WAVE - 1) wsum[wave] = incl;
-        __syncthreads();
-        int before = 0, all = 0;
-#pragma unroll
-        for (int k = 0; k < GEOM_SCAN / GEOM_WAVE; ++k) {
-            const int t = wsum[k];
-            before += k < wave ? t : 0;
-            all += t;
-        }
-        if (i < n) s[i] = carry + before + incl - v;
-        carry += all;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) total[blockIdx.x] = carry;
-}
-
 // ------------------------------------------------------------------ triangles
 struct TriArgs {
     const uint8_t* mask;     // or NULL: every vertex inside
@@ -230,7 +166,7 @@ __global__ __launch_bounds__(GEOM_THREADS) void tri_kernel(TriArgs a, FastDiv ce
             // candidates in order: lane 0's first, lane 0's second, lane 1's first, ...
             const int below = lanes_below(b0) + lanes_below(b1);
             int round_total;
-            const int before = waves_before(lds, __popcll(b0) + __popcll(b1), round_total);
+            const int before = waves_before<GEOM_WAVES>(lds, __popcll(b0) + __popcll(b1), round_total);
             long p = pos + before + below;
             const int tl = (int)cy * a.w + (int)cx, tr = tl + 1, bl = tl + a.w, br = bl + 1;
             if ((f & 1) && p < a.capacity) { out[3 * p] = tl; out[3 * p + 1] = bl; out[3 * p + 2] = tr; }
@@ -240,11 +176,8 @@ __global__ __launch_bounds__(GEOM_THREADS) void tri_kernel(TriArgs a, FastDiv ce
         }
     }
     if (!SCATTER) {
-        int wave_total = mine;
-#pragma unroll
-        for (int d = GEOM_WAVE / 2; d > 0; d >>= 1) wave_total += __shfl_xor(wave_total, d, GEOM_WAVE);
         int total;
-        waves_before(lds, wave_total, total);
+        waves_before<GEOM_WAVES>(lds, wave_total(mine), total);
         if (threadIdx.x == 0) a.sums[(long)b * a.nblk + blockIdx.x] = total;
     }
 }
@@ -300,10 +233,8 @@ __global__ __launch_bounds__(GEOM_THREADS) void vertex_kernel(CompactArgs a) {
         if (!GATHER) {
             mine += m;
         } else {
-            const uint64_t bal = __ballot(m);
             int round_total;
-            const int before = waves_before(lds, __popcll(bal), round_total);
-            const long p = pos + before + lanes_below(bal);
+            const long p = pos + block_excl_flag<GEOM_WAVES>(m, lds, round_total);
             if (v < a.hw) index[v] = m ? (int32_t)p : -1;
             if (m && p < a.vertex_capacity) {
                 const T* src = (const T*)a.points + ((long)b * a.hw + v) * 3;
@@ -319,11 +250,8 @@ __global__ __launch_bounds__(GEOM_THREADS) void vertex_kernel(CompactArgs a) {
         }
     }
     if (!GATHER) {
-        int wave_total = mine;
-#pragma unroll
-        for (int d = GEOM_WAVE / 2; d > 0; d >>= 1) wave_total += __shfl_xor(wave_total, d, GEOM_WAVE);
         int total;
-        waves_before(lds, wave_total, total);
+        waves_before<GEOM_WAVES>(lds, wave_total(mine), total);
         if (threadIdx.x == 0) a.sums[(long)b * a.nblk + blockIdx.x] = total;
     }
 }
@@ -355,12 +283,9 @@ extern "C" int ada_mesh_triangles_fwd(const uint8_t* mask, int64_t row_pitch_byt
                                       int32_t capacity, int32_t* count, void* workspace, int64_t workspace_bytes, void* stream) {
     ADA_REQUIRE(count && workspace && (triangles || capacity == 0), ADA_EINVAL, "ada_mesh_triangles_fwd: null pointer");
     ADA_REQUIRE(geom_shape_ok(batch, h, w), ADA_EINVAL, "ada_mesh_triangles_fwd: batch=%d h=%d w=%d outside 1..65535 / h * w < 2^30", batch, h, w);
-    ADA_REQUIRE(capacity >= 0 && (int64_t)batch * capacity * 3 < ((int64_t)1 << 40), ADA_EINVAL, "ada_mesh_triangles_fwd: capacity=%d", capacity);
-    ADA_REQUIRE(inverse == 0 || inverse == 1, ADA_EINVAL, "ada_mesh_triangles_fwd: inverse=%d (0 or 1)", inverse);
-    ADA_REQUIRE(!mask || (row_pitch_bytes >= w && (batch == 1 || image_stride_bytes >= (int64_t)(h - 1) * row_pitch_bytes + w)), ADA_EINVAL,
-                "ada_mesh_triangles_fwd: mask pitch %ld / stride %ld too small for %d x %d", (long)row_pitch_bytes, (long)image_stride_bytes, h, w);
-    ADA_REQUIRE(!(max_ratio > 0.0) || depth, ADA_EINVAL, "ada_mesh_triangles_fwd: max_ratio needs the depth map");
-    ADA_REQUIRE(max_ratio == max_ratio, ADA_EINVAL, "ada_mesh_triangles_fwd: max_ratio is NaN");
+    const int rc = mesh_rule_check("ada_mesh_triangles_fwd", mask, row_pitch_bytes, image_stride_bytes, inverse, max_ratio, batch, h, w, capacity);
+    if (rc != ADA_OK) return rc;
+    ADA_REQUIRE(!(max_ratio > 0.0) || depth, ADA_EINVAL, "ada_mesh_triangles_fwd: max_ratio needs the depth map");      // a NaN ratio never gets here
     const int64_t ncells = (int64_t)(h - 1) * (w - 1);
     const int64_t nblk = (ncells + GEOM_CHUNK - 1) / GEOM_CHUNK;
     const int64_t need = 4 * (int64_t)batch * (nblk > 0 ? nblk : 1);
@@ -374,7 +299,7 @@ extern "C" int ada_mesh_triangles_fwd(const uint8_t* mask, int64_t row_pitch_byt
     const FastDiv per_row = make_fastdiv((uint32_t)(w - 1));
     const dim3 grid((unsigned)nblk, (unsigned)batch);
     if (nblk > 0) hipLaunchKernelGGL(tri_kernel<false>, grid, dim3(GEOM_THREADS), 0, s, t, per_row);
-    hipLaunchKernelGGL(scan_kernel, dim3((unsigned)batch), dim3(GEOM_SCAN), 0, s, t.sums, (int)nblk, (long)nblk, count);
+    hipLaunchKernelGGL(scan_sums_kernel<1>, dim3((unsigned)batch), dim3(SCAN_THREADS), 0, s, t.sums, (long)nblk, (long)nblk, count);
     if (nblk > 0 && capacity > 0) hipLaunchKernelGGL(tri_kernel<true>, grid, dim3(GEOM_THREADS), 0, s, t, per_row);
     return ada_check_launch("ada_mesh_triangles_fwd");
 }
@@ -404,7 +329,7 @@ extern "C" int ada_mesh_compact_fwd(int32_t* triangles, const int32_t* count, in
     const dim3 vgrid((unsigned)nblk, (unsigned)batch);
     if (capacity > 0) hipLaunchKernelGGL(tri_index_kernel<true>, tgrid, dim3(GEOM_THREADS), 0, s, c);
     hipLaunchKernelGGL((vertex_kernel<false, float>), vgrid, dim3(GEOM_THREADS), 0, s, c);
-    hipLaunchKernelGGL(scan_kernel, dim3((unsigned)batch), dim3(GEOM_SCAN), 0, s, c.sums, (int)nblk, (long)nblk, vertex_count);
+    hipLaunchKernelGGL(scan_sums_kernel<1>, dim3((unsigned)batch), dim3(SCAN_THREADS), 0, s, c.sums, (long)nblk, (long)nblk, vertex_count);
     if (point_bytes == 8) hipLaunchKernelGGL((vertex_kernel<true, double>), vgrid, dim3(GEOM_THREADS), 0, s, c);
     else hipLaunchKernelGGL((vertex_kernel<true, float>), vgrid, dim3(GEOM_THREADS), 0, s, c);
     if (capacity > 0) hipLaunchKernelGGL(tri_index_kernel<false>, tgrid, dim3(GEOM_THREADS), 0, s, c);

@@ -14,16 +14,18 @@
 //   2 cc_border_kernel   unions every neighbour pair that straddles a tile border, the diagonal pairs at tile corners included (8-connectivity)
 //   3 cc_resolve_kernel  every tile-local root chases to its global root (read-only: nothing is written that another thread reads); root flags
 //                        are counted per chunk of 1024 consecutive pixels
-//   4 cc_scan_kernel     exclusive scan of the chunk counts, one workgroup per image; writes n_labels
-//   5 cc_number_kernel   roots get base + rank inside the chunk + 1, the background 0
+//   4 scan_sums_kernel   (ada_scan.h) exclusive scan of the chunk counts, one workgroup per image; writes n_labels
+//   5 cc_number_kernel   roots get base + rank inside the chunk + 1 (ada_scan.h's block_excl_flag), the background 0
 //   6 cc_paint_kernel    every other pixel copies its root's number
 // Integer atomics only, no scratch (csrc/build.py NO_SCRATCH), nothing allocated.
-#include "ada_common.h"
+#include "ada_scan.h"
 
 namespace {
 
 constexpr int CC_T = 32;           // tile edge: 1024 pixels, one per thread
-constexpr int CC_CHUNK = 1024;     // pixels per chunk of the root count
+constexpr int CC_CHUNK = 1024;     // pixels per chunk of the root count, one per thread
+constexpr int CC_WAVES = CC_CHUNK / ADA_WAVE;
+constexpr int CC_SCAN_ITEMS = 1;   // chunk counts per thread and step of the scan
 constexpr int CC_STRIP = 64;       // pixels of one row walked by one thread of the run kernels
 #define CC_WG __HIP_MEMORY_SCOPE_WORKGROUP
 #define CC_AGENT __HIP_MEMORY_SCOPE_AGENT
@@ -148,24 +150,6 @@ __global__ __launch_bounds__(256) void cc_border_kernel(int* par_all, int h, int
     }
 }
 
-// number of set flags of the block (returned to every thread) and, through `before`, of the threads in front of this one; block 1024
-ADA_DEV int block_rank(bool flag, int& before) {
-    __shared__ int wave_count[CC_CHUNK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(flag);
-    if (lane == 0) wave_count[wave] = __popcll(bal);
-    __syncthreads();
-    int total = 0, front = 0;
-#pragma unroll
-    for (int k = 0; k < CC_CHUNK / 64; ++k) {
-        const int c = wave_count[k];
-        front += k < wave ? c : 0;
-        total += c;
-    }
-    before = front + __popcll(bal & ((1ull << lane) - 1ull));
-    return total;
-}
-
 // Phase 3.  Block 1024 = one chunk of consecutive pixels, grid (chunks, batch).  Only tile-local roots chase (the other pixels are one hop from
 // theirs); nothing the chase reads is written in this launch.  The chase strictly decreases: at most i steps.
 __global__ __launch_bounds__(1024) void cc_resolve_kernel(const int* par_all, int* aux_all, int* chunk_count, long hw, int nchunks) {
@@ -181,37 +165,10 @@ __global__ __launch_bounds__(1024) void cc_resolve_kernel(const int* par_all, in
             root = r == (int)i;
         }
     }
-    int before;
-    const int total = block_rank(root, before);
+    __shared__ int lds[CC_WAVES];
+    int total;
+    block_excl_flag<CC_WAVES>(root, lds, total);
     if (threadIdx.x == 0) chunk_count[(long)blockIdx.y * nchunks + blockIdx.x] = total;
-}
-
-// Phase 4.  One block of 1024 per image: thread t owns a contiguous slice of the chunk counts, the slice sums are scanned in LDS, the counts are
-// replaced by their exclusive prefix.  Thread 1023 holds the total.
-__global__ __launch_bounds__(1024) void cc_scan_kernel(int* chunk_all, int nchunks, int* n_labels) {
-    __shared__ int sh[1024];
-    int* c = chunk_all + (long)blockIdx.x * nchunks;
-    const int tid = threadIdx.x;
-    const int per = (nchunks + 1023) / 1024;
-    const int lo = tid * per < nchunks ? tid * per : nchunks;
-    const int hi = lo + per < nchunks ? lo + per : nchunks;
-    int s = 0;
-    for (int j = lo; j < hi; ++j) s += c[j];
-    sh[tid] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int t = tid >= off ? sh[tid - off] : 0;
-        __syncthreads();
-        sh[tid] += t;
-        __syncthreads();
-    }
-    int base = sh[tid] - s;
-    for (int j = lo; j < hi; ++j) {
-        const int t = c[j];
-        c[j] = base;
-        base += t;
-    }
-    if (tid == 1023) n_labels[blockIdx.x] = sh[1023];
 }
 
 // Phase 5: the roots' numbers and the background's 0.  A thread writes its own pixel only.
@@ -219,8 +176,9 @@ __global__ __launch_bounds__(1024) void cc_number_kernel(const int* par_all, con
     const long i = (long)blockIdx.x * CC_CHUNK + threadIdx.x;
     const int v = i < hw ? par_all[(long)blockIdx.y * hw + i] : -1;
     const bool root = i < hw && v == (int)i;
-    int before;
-    block_rank(root, before);
+    __shared__ int lds[CC_WAVES];
+    int total;
+    const int before = block_excl_flag<CC_WAVES>(root, lds, total);      // every thread of the workgroup: the return comes after it
     if (i >= hw) return;
     if (root) labels_all[(long)blockIdx.y * hw + i] = chunk_base[(long)blockIdx.y * nchunks + blockIdx.x] + before + 1;
     else if (v == -1) labels_all[(long)blockIdx.y * hw + i] = 0;
@@ -466,7 +424,7 @@ extern "C" int ada_mask_label_fwd(const uint8_t* mask, int32_t batch, int32_t h,
     hipLaunchKernelGGL(cc_tile_kernel, dim3((unsigned)tiles, (unsigned)batch), dim3(CC_T * CC_T), 0, s, t);
     hipLaunchKernelGGL(cc_border_kernel, dim3(blocks_of(hw, 256), (unsigned)batch), dim3(256), 0, s, par, h, w, (long)hw, t.conn8);
     hipLaunchKernelGGL(cc_resolve_kernel, dim3((unsigned)nchunks, (unsigned)batch), dim3(CC_CHUNK), 0, s, par, aux, chunks, (long)hw, nchunks);
-    hipLaunchKernelGGL(cc_scan_kernel, dim3((unsigned)batch), dim3(1024), 0, s, chunks, nchunks, n_labels);
+    hipLaunchKernelGGL(scan_sums_kernel<CC_SCAN_ITEMS>, dim3((unsigned)batch), dim3(SCAN_THREADS), 0, s, chunks, (long)nchunks, (long)nchunks, n_labels);
     hipLaunchKernelGGL(cc_number_kernel, dim3((unsigned)nchunks, (unsigned)batch), dim3(CC_CHUNK), 0, s, par, chunks, labels, (long)hw, nchunks);
     hipLaunchKernelGGL(cc_paint_kernel, dim3(blocks_of(hw, 256), (unsigned)batch), dim3(256), 0, s, par, aux, labels, (long)hw);
     return ada_check_launch("ada_mask_label_fwd");

@@ -13,7 +13,7 @@
 // regions (a saturated sigmoid, a clipped ReLU); unaggregated, their 64 adds to one LDS word serialise.
 //
 // Launches: one clear of the workspace (a kernel, not a memset node: every node of a capture is then a kernel of this file), four passes, one finish -- fixed by (batch, n) alone, nothing read back: legal inside a stream capture.
-#include "ada_common.h"
+#include "ada_scan.h"
 
 namespace {
 
@@ -84,7 +84,7 @@ ADA_DEV void rank_pair(int mode, double q, uint32_t cnt, uint32_t& j0, uint32_t&
 }
 
 // Decides pass s (its bins are complete: the kernel before this one wrote them) for every rank: the bucket that holds the rank and the rank's offset
-// inside it.  Wave w takes ranks w and w + 4; a lane owns four consecutive bins, the wave scans the 64 sums.  Leaves the state in `sh`, the distinct
+// inside it.  Wave w takes ranks w and w + 4; a lane owns four consecutive bins, the wave scans the 64 sums (ada_scan.h's wave_incl_scan).  Leaves the state in `sh`, the distinct
 // prefixes as slots; both barriers are in here.  Pass 0 has no earlier state: its ranks come from the count it produced.
 __device__ void decide(const QArgs& a, uint32_t* wsb, int s, QShared& sh, bool publish) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -99,12 +99,7 @@ __device__ void decide(const QArgs& a, uint32_t* wsb, int s, QShared& sh, bool p
         }
         const uint4 h = *reinterpret_cast<const uint4*>(wsb + ((s * Q_RANKS + (int)slot) * 256 + 4 * lane));
         const uint32_t sum = h.x + h.y + h.z + h.w;
-        uint32_t incl = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d);
-            if (lane >= d) incl += up;
-        }
+        const uint32_t incl = wave_incl_scan(sum);
         if (s == 0) {
             const uint32_t cnt = __shfl(incl, 63) + st[Q_ST_NAN];
             uint32_t j0, j1;

@@ -20,18 +20,18 @@
 //                             k, k + teams, ...: two screen-filling triangles get half the device each, and among thousands of large triangles no
 //                             workgroup reads more than its team's share of setups and none has a whole screen to itself.
 // A tile is one sample per thread and is rejected as a whole when one edge function is negative at all four of its corners (the functions are linear).
-// Appending is one ballot per class and wave and one counter add by its first flagged lane; the order of the list cannot reach the output.  The
+// Appending is one ballot per class and wave and one counter add by its first flagged lane (wave_append, on ada_scan.h's lanes_below).  The
 // walking launch has a fixed grid; no launch's running time depends on one thread's triangle.
 //
 // Resolve.  One thread per pixel recomputes the winner's edge functions and fp64 interpolants from its id and writes index, depth and colour.
 //
 // Clear, bin, walk, resolve: four launches fixed by the shapes alone, nothing read back: legal inside a stream capture.
-#include "ada_common.h"
+#include "ada_scan.h"
 
 namespace {
 
 constexpr int RAST_THREADS = 256;
-constexpr int RAST_WAVE = 64;
+constexpr int RAST_WAVE = ADA_WAVE;
 constexpr int SMALL_MAX = ADA_RASTER_SMALL_MAX;
 constexpr int WAVE_MAX = ADA_RASTER_WAVE_MAX;
 constexpr int TILE_W = ADA_RASTER_TILE_W, TILE_H = ADA_RASTER_TILE_H;      // a workgroup's tile
@@ -161,11 +161,8 @@ ADA_DEV void candidate(const RasterArgs& a, const Tri& t, int id, int j, int i) 
     __hip_atomic_fetch_max(p, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-ADA_DEV int lanes_below(uint64_t ballot) {
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-}
-
-// one ballot, one counter add by the wave's first flagged lane; returns this lane's position in the class (meaningful where flag is set)
+// one ballot, one counter add by the wave's first flagged lane; returns this lane's position in the class (meaningful where flag is set).  An atomic
+// append on purpose, unlike the ordered compaction of ada_scan.h, from which it takes only lanes_below: the order of the list cannot reach the output
 ADA_DEV int wave_append(int32_t* counter, bool flag) {
     const uint64_t bal = __ballot(flag);
     if (bal == 0) return 0;

@@ -85,6 +85,23 @@ def test_triangles_count_and_error_map_equal_the_restatement(hip, shape):
         _check(G, d, kw, want, E)
 
 
+def test_more_sums_than_one_step_of_the_scan(hip):
+    """417 x 993: 13 x 31 cells of 32, 806 subtrees under N = 1024, 10 + 11 * 806 = 8 876 sums, more than the 1024 * 8 of one step of the scan: the
+    leaf-level sums of the whole last row of cells get their offsets from the carry, and max_error = 0.0 emits every leaf there."""
+    import os
+    import re
+    from hip_ext import geometry as G
+    h, w = 417, 993
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "amodal-depth-anything_amd", "csrc", "ada_adaptive.hip")
+    step = 1024 * int(re.search(r"constexpr int AD_SCAN_ITEMS = (\d+);", open(src).read()).group(1))
+    cell, log_n = hip.ADAPT_CELL, int(np.ceil(np.log2(max(h, w) - 1)))
+    lb, levels = 2 * (log_n - int(np.log2(cell))), 2 * log_n + 1
+    n_sub = 2 * -(-(h - 1) // cell) * -(-(w - 1) // cell)
+    assert (cell, log_n, n_sub) == (32, 10, 806) and lb + (levels - lb) * n_sub > step
+    d, kw, want, E = _ref(h, w, "plain")
+    _check(G, d, kw, want, E)
+
+
 @pytest.mark.parametrize("shape", ((3, 2), (12, 19), (70, 53)), ids=lambda s: f"{s[0]}x{s[1]}")
 def test_mask_forms(hip, shape):
     """bool, a numpy mask, and a pitched crop of a larger tensor read in place."""

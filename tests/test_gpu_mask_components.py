@@ -60,6 +60,32 @@ def test_labels_at_518(hip, conn):
     _check_labels(M, [R.random_mask(518, 518, 0.59, 7), R.ellipse(518, 518, 280, 230, 120, 150)], conn)
 
 
+def _chunk_scan_step():
+    """Chunk counts that one step of the labelling's scan takes: 1024 threads times the items per thread that csrc/ada_masks.hip instantiates."""
+    import os
+    import re
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "amodal-depth-anything_amd", "csrc", "ada_masks.hip")
+    return 1024 * int(re.search(r"constexpr int CC_SCAN_ITEMS = (\d+);", open(src).read()).group(1))
+
+
+@pytest.mark.parametrize("steps,more", ((1, -1), (1, 0), (1, 1), (2, 1)), ids=("step-1", "step", "step+1", "2step+1"))
+def test_labels_where_the_chunk_scan_carries_between_steps(hip, steps, more):
+    """A row of 1024 pixels is one chunk of the root count, so the rows are the sums of the scan: one short of a step, a step, one more (the first
+    carry) and two steps and one (a carry into a carry).  Isolated pixels only -- a seeded half of the lattice [::2, ::2], each its own component under
+    either connectivity -- so a chunk's count differs from its neighbours' and the labels are the running count of the mask in raster order."""
+    from hip_ext import masks as M
+    h, w = steps * _chunk_scan_step() + more, 1024
+    mask = np.zeros((h, w), np.uint8)
+    mask[::2, ::2] = np.random.default_rng(h).random(((h + 1) // 2, w // 2)) < 0.5
+    want = np.cumsum(mask.ravel(), dtype=np.int64).reshape(h, w) * mask
+    per_chunk = mask.sum(axis=1)
+    assert per_chunk.min() < per_chunk.max() and int(want.max()) == int(mask.sum()) < 2 ** 31
+    for conn in (4, 8):
+        comp = M.connected_components(mask, connectivity=conn, stats=False)
+        assert comp.count.tolist() == [int(mask.sum())], conn
+        assert np.array_equal(comp.labels[0].cpu().numpy(), want), conn
+
+
 @pytest.mark.parametrize("conn", [4, 8])
 def test_labels_of_the_structured_masks(hip, conn):
     from hip_ext import masks as M
