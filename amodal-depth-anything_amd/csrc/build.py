@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)     # isa_guard.py lives next to this file: the package builds without the repository's tools/
-SOURCES = ["ada_api.hip", "ada_igemm.hip", "ada_attention.hip", "ada_elementwise.hip", "ada_pipeline.hip", "ada_eval.hip", "ada_tail.hip", "ada_image.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip", "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip"]
+SOURCES = ["ada_api.hip", "ada_igemm.hip", "ada_attention.hip", "ada_elementwise.hip", "ada_pipeline.hip", "ada_eval.hip", "ada_tail.hip", "ada_image.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip", "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip", "ada_inpaint.hip"]
 HEADERS = ["ada_common.h", "ada_scan.h", "ada_mesh_rule.h", "ada_igemm_pipe4.inc", os.path.join("..", "..", "include", "ada_hip.h")]
 ARCH = "gfx950"
 # ada_tail.hip: no SLP vectorisation.  Vectorised, the producers' interpolation becomes v_pk_mul_f32 / v_pk_fma_f32 on register pairs
@@ -35,8 +35,11 @@ ARCH = "gfx950"
 # include/ada_hip.h, which holds only when every product, sum and quotient is rounded on its own; the kernels spell it with __dmul_rn / __dadd_rn.
 # ada_adaptive.hip: no contraction.  The error map of the adaptive mesh is compared bit for bit with tests/_adaptive_ref.py: 0.5 (omega_a + omega_b) - omega_m
 # and the inverse mode's a depth + b must not turn into FMAs.
+# ada_inpaint.hip: no contraction.  The push-pull fill is compared bit for bit with the float32 numpy restatement in tests/_inpaint_ref.py: the masked means
+# ((s00 + s01) + s10) + s11 and the interpolation ((9 a + 3 b) + 3 c) + d round every product and every sum on their own.
 PER_FILE_FLAGS = {"ada_tail.hip": ["-fno-slp-vectorize"], "ada_igemm.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"], "ada_geometry.hip": ["-ffp-contract=off"],
-                  "ada_edges.hip": ["-ffp-contract=off"], "ada_raster.hip": ["-ffp-contract=off"], "ada_adaptive.hip": ["-ffp-contract=off"]}
+                  "ada_edges.hip": ["-ffp-contract=off"], "ada_raster.hip": ["-ffp-contract=off"], "ada_adaptive.hip": ["-ffp-contract=off"],
+                  "ada_inpaint.hip": ["-ffp-contract=off"]}
 # ada_igemm.hip joined in round 4: a by-reference lambda capture of the k-walk counters put them into scratch behind the loop's "memory"-clobbering
 # waits -- 12 bytes reloaded every k-step of every GEMM, silently, for most of a round.  No kernel of these files may use scratch or spill VGPRs.
 # ada_image.hip / ada_pipeline.hip hold no hand-managed loads: their kernels are single memory-bound passes, one thread per output pixel, where any
@@ -58,8 +61,10 @@ PER_FILE_FLAGS = {"ada_tail.hip": ["-fno-slp-vectorize"], "ada_igemm.hip": ["-fn
 # ada_adaptive.hip: a triangle is six integer coordinates in scalars, decoded from its heap index by a loop over the path bits; no per-thread array.
 # ada_filters.hip: a thread's window stays in LDS and its rank is selected bit by bit with counters in registers; a window copied into a per-thread array
 # (a sorting network indexed at run time) would live in scratch.
+# ada_inpaint.hip: a thread owns one pixel; the row pass keeps its running minimum (a distance and a position) in two registers and reads the candidates from
+# LDS, the pyramid's four children and four parents are named scalars.  The level table of the push-pull fill is a host array, never a kernel's.
 NO_SCRATCH = {"ada_tail.hip", "ada_igemm.hip", "ada_image.hip", "ada_pipeline.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip",
-              "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip"}
+              "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip", "ada_inpaint.hip"}
 # Round 4: the wrong results above were root-caused (profiles/r04_a_tail_inflight_register_root_cause.txt) -- NOT a hardware hazard of packed
 # fp32 beside MFMAs (tools/ubench/pk_f32_beside_mfma.hip: 0 mismatches) but the compiler copying registers that the kernel's inline-asm
 # fetches were still writing: with SLP on, the allocator parks a source row in other registers with v_mov_b64 placed ABOVE the hand-counted

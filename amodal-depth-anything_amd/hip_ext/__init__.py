@@ -864,6 +864,64 @@ def extreme_filter_fwd(x, kh, kw, rank, border, out, valid=None, fill=0.0, count
                                          _stream()), "ada_extreme_filter_fwd")
 
 
+def nearest_valid_workspace_bytes(batch: int, h: int, w: int) -> int:
+    """Bytes of workspace ada_nearest_valid_fwd asks for (ada_nearest_valid_workspace_bytes): one int32 per pixel."""
+    n = ctypes.c_int64(0)
+    _check(load().ada_nearest_valid_workspace_bytes(int(batch), int(h), int(w), ctypes.byref(n)), "ada_nearest_valid_workspace_bytes")
+    return n.value
+
+
+def push_pull_workspace_bytes(batch: int, channels: int, h: int, w: int) -> int:
+    """Bytes of workspace ada_push_pull_fwd asks for (ada_push_pull_workspace_bytes): the pyramid above level 0, 0 for a 1 x 1 image."""
+    n = ctypes.c_int64(0)
+    _check(load().ada_push_pull_workspace_bytes(int(batch), int(channels), int(h), int(w), ctypes.byref(n)), "ada_push_pull_workspace_bytes")
+    return n.value
+
+
+def _planes4(who, x, name="x"):
+    """Shape of a non-empty contiguous fp32 [B, C, h, w] device tensor."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or not x.is_contiguous() or x.numel() == 0:
+        raise HipExtError(f"{who}: {name} must be a non-empty contiguous [B, C, h, w] tensor, got {tuple(getattr(x, 'shape', ()))}")
+    _dev(x, name, torch.float32)
+    return tuple(x.shape)
+
+
+def nearest_valid_fwd(valid, index, dist2=None, workspace=None):
+    """valid uint8 [B, h, w] -> index int32 [B, h, w]: the flat position of the nearest valid pixel of the same image, ties to the smallest flat position,
+    -1 where the image has none (ada_nearest_valid_fwd).  ``dist2``: optional int32 [B, h, w], the exact squared distance (0x7fffffff where the image
+    has none).  ``workspace``: at least nearest_valid_workspace_bytes(B, h, w) bytes, allocated when None."""
+    who = "nearest_valid_fwd"
+    B, h, w = _maps3(who, valid, "valid", torch.uint8)
+    pi = _like(who, "index", index, valid, torch.int32)
+    pd = _like(who, "dist2", dist2, valid, torch.int32, optional=True)
+    ws, ws_bytes = _bytes_of(who, workspace, nearest_valid_workspace_bytes(B, h, w), valid.device)
+    _check(load().ada_nearest_valid_fwd(valid.data_ptr(), B, h, w, pi, pd, ws.data_ptr(), ws_bytes, _stream()), "ada_nearest_valid_fwd")
+
+
+def fill_gather(x, valid, index, out, empty=0.0):
+    """out[b, c, p] = valid[b, p] ? x[b, c, p] : (index[b, p] >= 0 ? x[b, c, index[b, p]] : empty), bit for bit (ada_fill_gather_fwd).  x, out fp32
+    [B, C, h, w]; valid uint8 and index int32 [B, h, w]."""
+    who = "fill_gather"
+    B, C, h, w = _planes4(who, x)
+    po = _like(who, "out", out, x, torch.float32)
+    pv = _sized(who, "valid", valid, (B, h, w), torch.uint8)
+    pi = _sized(who, "index", index, (B, h, w), torch.int32)
+    _same_device(who, "x", x, valid=valid, index=index)
+    _check(load().ada_fill_gather_fwd(x.data_ptr(), pv, pi, B, C, h, w, float(empty), po, _stream()), "ada_fill_gather_fwd")
+
+
+def push_pull(x, valid, out, empty=0.0, workspace=None):
+    """x fp32 [B, C, h, w], valid uint8 [B, h, w] -> out: the push-pull fill of include/ada_hip.h's "Hole filling" section (ada_push_pull_fwd); valid
+    pixels carry x bit for bit.  ``workspace``: at least push_pull_workspace_bytes(B, C, h, w) bytes, allocated when None."""
+    who = "push_pull"
+    B, C, h, w = _planes4(who, x)
+    po = _like(who, "out", out, x, torch.float32)
+    pv = _sized(who, "valid", valid, (B, h, w), torch.uint8)
+    _same_device(who, "x", x, valid=valid)
+    ws, ws_bytes = _bytes_of(who, workspace, push_pull_workspace_bytes(B, C, h, w), x.device)
+    _check(load().ada_push_pull_fwd(x.data_ptr(), pv, B, C, h, w, float(empty), po, ws.data_ptr() if ws_bytes else None, ws_bytes, _stream()), "ada_push_pull_fwd")
+
+
 # --- tuning / diagnostic hooks (include/ada_hip.h, last section) ---------------------------------
 TILE_NAMES = {0: "256x32", 1: "128x64", 2: "256x128", 3: "256x256", 4: "128x128"}
 

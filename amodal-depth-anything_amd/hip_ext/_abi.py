@@ -72,6 +72,8 @@ FILTER_MAX_WINDOW = 81
 FILTER_MAX_EXTREME = 63
 FILTER_TILE_W, FILTER_TILE_H = 64, 4
 FILTER_COL_TILE_H = 16
+# ada_nearest_valid_fwd: columns of a row staged per step of the row pass
+INPAINT_CHUNK = 1024
 
 
 class IgemmArgs(ctypes.Structure):
@@ -177,6 +179,11 @@ PROTOTYPES = {
     "ada_rank_filter_fwd": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, c_void_p, c_void_p, c_void_p]),
     "ada_extreme_filter_fwd": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_void_p]),
+    "ada_nearest_valid_workspace_bytes": (c_int, [c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "ada_nearest_valid_fwd": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ada_fill_gather_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p]),
+    "ada_push_pull_workspace_bytes": (c_int, [c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "ada_push_pull_fwd": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
     "ada_tile_blend_fwd": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "ada_selftest": (c_int, [c_void_p, c_int64, c_void_p]),
     "ada_debug_set_tile": (None, [c_int]),

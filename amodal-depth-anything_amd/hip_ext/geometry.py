@@ -23,6 +23,8 @@ import torch
 
 from . import (HipExtError, RASTER_OUT_NORMALISED, RASTER_OUT_W, RASTER_OUT_Z, depth_points, mesh_adaptive, mesh_adaptive_workspace_bytes, mesh_compact,
                mesh_project, mesh_raster, mesh_raster_workspace_bytes, mesh_triangles)
+from . import inpaint as _inpaint
+from . import masks as _masks
 from ._staging import as_int, check_planar, from_numpy, resolve_device, stage_planar
 
 Mesh = namedtuple("Mesh", "points triangles vertex_count triangle_count colors")
@@ -534,6 +536,66 @@ def render_layers(layers, h, w, objects=None, scene=True, near=1.0, far=10.0, ou
     labels = ([0] if scene else []) + [k + 1 for k in chosen]
     inverse = (1.0 / near - 1.0 / far, 1.0 / far)
     return _render(who, [(m.points, m.triangles, m.colors) for m in meshes], labels, h, w, K, fov_deg, R, t, out, inverse, fill, fill_color, device)
+
+
+_FILLS = ("smooth", "nearest")
+
+
+def _fill_fn(who, method):
+    if method not in _FILLS:
+        raise ValueError(f"{who}: method must be 'smooth' or 'nearest', got {method!r}")
+    return _inpaint.fill_smooth if method == "smooth" else _inpaint.fill_nearest
+
+
+@torch.no_grad()
+def fill_view(view, method="smooth") -> View:
+    """The view with its holes filled: the pixels no triangle covered (``view.owner < 0``) get depth, and colour where ``view.color`` is not None, from
+    the pixels a triangle covered -- hip_ext.inpaint.fill_smooth (``method='smooth'``, the push-pull fill) or fill_nearest (``'nearest'``, the value of
+    the nearest covered pixel).  Covered pixels keep their bits; ``index`` and ``owner`` are returned unchanged, so the caller still sees which pixels
+    were holes.  A view without any covered pixel comes back unchanged.  The fill interpolates what is seen and knows nothing of the geometry behind a
+    hole.  Nothing is read back: the empty view is kept by a select on the device."""
+    who = "fill_view"
+    if not isinstance(view, View):
+        raise TypeError(f"{who}: a View expected, got {type(view).__name__}")
+    fill = _fill_fn(who, method)
+    valid = view.owner >= 0
+    some = valid.any()
+    depth = torch.where(some, fill(view.depth, valid), view.depth)
+    color = None if view.color is None else torch.where(some, fill(view.color, valid), view.color)
+    return View(depth, view.index, view.owner, color)
+
+
+@torch.no_grad()
+def remove_objects(depth, masks, image=None, grow=1, method="smooth", device=None):
+    """(depth_filled, image_filled or None): the depth map, and the photo when given, with the objects under ``masks`` taken out.  The union of ``masks``
+    (uint8 / bool [K, h, w] or [h, w], non-zero = object) is dilated ``grow`` times with hip_ext.masks.dilate(size=3) (``grow=0``: not at all), marked
+    invalid and filled from the rest with hip_ext.inpaint.fill_smooth / fill_nearest (``method``).  Pixels outside the grown union keep their bits.
+    ``depth``: fp32 [h, w]; ``image``: uint8 [h, w, 3] or None.  Through depth_to_mesh the result is a background layer to render behind amodal_layers'
+    objects.  This is geometry-blind interpolation of the surroundings, not a learned completion: what stood behind the objects is not recovered."""
+    who = "remove_objects"
+    fill = _fill_fn(who, method)
+    h, w, was2d = _check_depth(who, depth)
+    if not was2d:
+        raise ValueError(f"{who}: depth must be [h, w], got shape {tuple(depth.shape)}")
+    _check_mask(who, masks)
+    if tuple(masks.shape[-2:]) != (h, w):
+        raise ValueError(f"{who}: masks of shape {tuple(masks.shape)} for a depth map of shape {(h, w)}")
+    if image is not None and (not isinstance(image, (np.ndarray, torch.Tensor)) or str(image.dtype).replace("torch.", "") != "uint8"
+                              or tuple(image.shape) != (h, w, 3)):
+        raise ValueError(f"{who}: image must be uint8 [{h}, {w}, 3], got {getattr(image, 'dtype', type(image).__name__)} {tuple(getattr(image, 'shape', ()))}")
+    g = as_int(grow)
+    if g is None or g < 0:
+        raise ValueError(f"{who}: grow must be a non-negative integer, got {grow!r}")
+    device = resolve_device(who, device, depth, masks, image)
+    with torch.cuda.device(device):
+        m = _stage_mask(who, masks, device)
+        union = (m != 0).any(dim=0).to(torch.uint8)
+        if g > 0:
+            union = _masks.dilate(union, size=3, iterations=g, device=device)
+        valid = union == 0
+        d = fill(_stage_depth(who, depth, device)[0], valid, device=device)
+        img = None if image is None else fill(image, valid, device=device)
+    return d, img
 
 
 def _host(a):

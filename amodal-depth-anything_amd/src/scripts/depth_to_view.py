@@ -3,12 +3,15 @@
 
     python -m src.scripts.depth_to_view DEPTH OUT.png [--mask MASK.png] [--inverse NEAR FAR] [--max_ratio R] [--fov 55] [--image PHOTO]
                                                      [--yaw D] [--pitch D] [--shift X Y Z] [--size H W] [--max_error E] [--median K]
+                                                     [--fill_holes {nearest,smooth}]
 
 DEPTH, ``--mask``, ``--inverse``, ``--max_ratio``, ``--max_error``, ``--median`` and ``--image`` are read as ``src.scripts.depth_to_mesh`` reads them.  The camera orbits by
 ``--yaw`` / ``--pitch`` degrees about the point on the optical axis at the map's median depth and then moves by ``--shift``
 (hip_ext.geometry.look_at_pose).  With ``--image`` the output is the photo-coloured view; without it, the view's depth through the colour map of
 hip_ext.image.colorize over the inverse depth (holes and background in its background grey).  ``--size`` renders at another size than the map's, with the same field
-of view.  Mesh, rasteriser and colour map run on the device; only the uint8 picture crosses to the host.
+of view.  ``--fill_holes`` gives the pixels no triangle covered a value from the covered ones before the picture is coloured
+(hip_ext.geometry.fill_view: ``smooth`` is the push-pull fill, ``nearest`` copies the nearest covered pixel); without it they keep the background.  Mesh,
+rasteriser, fill and colour map run on the device; only the uint8 picture crosses to the host.
 """
 import argparse
 import os
@@ -50,7 +53,7 @@ def pivot_depth(depth, ab=None) -> float:
 
 
 def view_file(src, dst, mask=None, inverse=None, max_ratio=None, fov=55.0, image=None, yaw=0.0, pitch=0.0, shift=(0.0, 0.0, 0.0), size=None,
-              device="cuda", max_error=None, median=None):
+              device="cuda", max_error=None, median=None, fill_holes=None):
     """Renders one file; returns the uint8 picture [H, W, 3] (R, G, B) that was written."""
     from hip_ext import image as hip_image
     ab = inverse_pair(inverse)
@@ -65,6 +68,8 @@ def view_file(src, dst, mask=None, inverse=None, max_ratio=None, fov=55.0, image
                                   max_ratio=max_ratio, max_error=max_error, median=median, device=device)
     R, t = geometry.look_at_pose(yaw, pitch, shift, pivot_z=pivot_depth(depth, ab))
     view = geometry.render_mesh(mesh, h, w, fov_deg=fov, R=R, t=t, out="w", fill=INVALID, device=device)
+    if fill_holes is not None:
+        view = geometry.fill_view(view, fill_holes)
     if view.color is not None:
         picture = view.color.cpu().numpy()
     else:
@@ -89,6 +94,7 @@ def build_parser():
     ap.add_argument("--size", type=int, nargs=2, metavar=("H", "W"), default=None, help="target size (default: the depth map's)")
     ap.add_argument("--max_error", type=float, default=None, help="adaptive mesh: the largest relative disparity error of a triangle that is not split (default: two triangles per cell)")
     ap.add_argument("--median", type=int, default=None, metavar="K", help="median-filter the depth over K x K windows (K odd) among the samples inside the mask before meshing: removes the flying pixels of occlusion borders")
+    ap.add_argument("--fill_holes", choices=("nearest", "smooth"), default=None, help="fill the pixels no triangle covered from the covered ones: the nearest covered pixel's value, or the smooth push-pull fill (default: they keep the background)")
     ap.add_argument("--device", default="cuda")
     return ap
 
@@ -96,7 +102,7 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
     picture = view_file(args.input, args.output, args.mask, args.inverse, args.max_ratio, args.fov, args.image, args.yaw, args.pitch, tuple(args.shift),
-                        args.size, args.device, args.max_error, args.median)
+                        args.size, args.device, args.max_error, args.median, args.fill_holes)
     print(f"{args.output}: {picture.shape[0]} x {picture.shape[1]}")
     return 0
 

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define ADA_ABI_VERSION 10   /* still 10: + ada_rank_filter_fwd, ada_extreme_filter_fwd (the rank filters; two more exports, no signature changed, so a caller built against the earlier 10 runs unchanged).  10: + ada_photo_prep_fwd, ada_mask_prep_fwd, ada_nearest_resize_fwd, ada_blend_ex (the amodal infer_image; exports only, no signature changed); later, still 10: + ada_depth_render_fwd (the rendering of infer.py:106-119; one more export, no signature changed, so a caller built against the earlier 10 runs unchanged).  History: 9: + ada_image_prep_fwd, ada_depth_resize_fwd (the raw model's infer_image; exports only, no signature changed).  History: 8 (round 6): the default-off experiment paths that lost are gone -- ada_igemm_args without ln_stats / ln_colsum / rowstat_out (EP_LNFOLD / EP_ROWSTATS) and the LayerNorm tail (ln_*), no ada_rowstats_finalize.  History: 6 (round 5): + ada_depth_stats_fwd, ada_token_diversity_fwd; 7: ada_igemm_args grows f8_from / f8_mid / f8_scales at its end and split_seg < 0 names the fp8 form of a split output (a zero-filled tail = off: every ABI-6 call means what it meant) */
+#define ADA_ABI_VERSION 10   /* still 10: + ada_nearest_valid_workspace_bytes, ada_nearest_valid_fwd, ada_fill_gather_fwd, ada_push_pull_workspace_bytes, ada_push_pull_fwd (hole filling; five more exports, no signature changed, so a caller built against the earlier 10 runs unchanged).  Earlier, still 10: + ada_rank_filter_fwd, ada_extreme_filter_fwd (the rank filters; two more exports, no signature changed, so a caller built against the earlier 10 runs unchanged).  10: + ada_photo_prep_fwd, ada_mask_prep_fwd, ada_nearest_resize_fwd, ada_blend_ex (the amodal infer_image; exports only, no signature changed); later, still 10: + ada_depth_render_fwd (the rendering of infer.py:106-119; one more export, no signature changed, so a caller built against the earlier 10 runs unchanged).  History: 9: + ada_image_prep_fwd, ada_depth_resize_fwd (the raw model's infer_image; exports only, no signature changed).  History: 8 (round 6): the default-off experiment paths that lost are gone -- ada_igemm_args without ln_stats / ln_colsum / rowstat_out (EP_LNFOLD / EP_ROWSTATS) and the LayerNorm tail (ln_*), no ada_rowstats_finalize.  History: 6 (round 5): + ada_depth_stats_fwd, ada_token_diversity_fwd; 7: ada_igemm_args grows f8_from / f8_mid / f8_scales at its end and split_seg < 0 names the fp8 form of a split output (a zero-filled tail = off: every ABI-6 call means what it meant) */
 
 /* status codes */
 #define ADA_OK 0
@@ -932,6 +932,47 @@ int ada_rank_filter_fwd(const void* x, const uint8_t* valid, int32_t dtype, int3
 int ada_extreme_filter_fwd(const void* x, const uint8_t* valid, int32_t dtype, int32_t batch, int32_t h, int32_t w, int32_t kh, int32_t kw,
                            int32_t rank, int32_t border, double fill, void* out, int32_t* count, void* workspace, int64_t workspace_bytes,
                            void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Hole filling: a pixel without a sample gets a value from the pixels that have one (additions under ABI 10).  The rasteriser paints what no triangle
+ * covers with a constant and the rank filters give a window without a valid sample a constant; these give every pixel a value.  The reference has no
+ * such operation.  valid: uint8 [batch][h][w] packed, non-zero = the pixel has a sample; one mask for all channels of an image.  x / out: fp32
+ * [batch][channels][h][w] packed.  batch, channels, h, w >= 1; h, w <= 32767 (else ADA_EUNSUPPORTED), batch <= 65535.
+ *   ada_nearest_valid_fwd    the Euclidean feature transform.  index int32 [batch][h][w] = the flat position r * w + c of the valid pixel of the same
+ *     image nearest in Euclidean distance; dist2 (optional, NULL: not written) int32 = the squared distance, an exact integer.  A valid pixel maps to
+ *     itself, distance 0.  TIE RULE: among equally near valid pixels the smallest flat position.  An image without a valid pixel: index = -1 and
+ *     dist2 = 0x7fffffff everywhere.  sqrt(dist2) is scipy.ndimage.distance_transform_edt(valid == 0); scipy's own index at a tie is an artefact of
+ *     its implementation and is not followed.
+ *     Work: a column pass (two scans) leaves per pixel the row of the nearest valid pixel of its column, the upper at equal |dy|; a row pass takes the
+ *     lexicographic minimum over x' of ((x - x')^2 + g(x')^2, r(x') w + x') with the row's pairs staged through LDS ADA_INPAINT_CHUNK columns at a time.
+ *     workspace  workspace_bytes >= ada_nearest_valid_workspace_bytes = 4 batch h w, 4-byte aligned  (checked)
+ *   ada_fill_gather_fwd      out[b][c][p] = valid[b][p] ? x[b][c][p] : (0 <= index[b][p] < h w ? x[b][c][index[b][p]] : empty).  Values move as
+ *     32-bit words: valid and copied pixels keep every bit.  index is ada_nearest_valid_fwd's; one outside the image counts as "none", never read.
+ *   ada_push_pull_fwd        the smooth multi-resolution fill.  Level 0 is h x w, level l + 1 is ceil(h_l / 2) x ceil(w_l / 2), the top level L is 1 x 1.
+ *     All in fp32, every product, sum and quotient rounded on its own (csrc/ada_inpaint.hip is built without floating-point contraction):
+ *     LEVEL 0  v = valid ? x : +0, m = valid ? 1 : 0, by a select: the value under an invalid pixel, NaN and inf included, never reaches a result.
+ *     PULL     coarse pixel (I, J) has the children (2 I + di, 2 J + dj), di, dj in {0, 1}; a child outside the level has m = 0.  n = the children
+ *              with m = 1; m' = n > 0; v' = n > 0 ? (((s00 + s01) + s10) + s11) / n : +0 with s = m ? v : +0 and a correctly rounded division.
+ *     TOP      a top pixel with m = 0 takes ``empty`` and counts as filled (an image without a valid pixel).
+ *     PUSH     top down.  A pixel (i, j) with m = 1 keeps v.  One with m = 0: I = i >> 1, I2 = clamp(I + (i & 1 ? 1 : -1), 0, h_{l+1} - 1), J and J2
+ *              likewise from j and w_{l+1}; v = (((9 a + 3 b) + 3 c) + d) * 0.0625 with a = V(I, J), b = V(I, J2), c = V(I2, J), d = V(I2, J2) of
+ *              the already pushed level above -- bilinear with half-pixel centres and clamped borders.  Every level is then completely filled.
+ *     out      level 0 after the push; valid pixels carry x bit for bit.
+ *     workspace  the pyramid above level 0: workspace_bytes >= ada_push_pull_workspace_bytes = batch (4 channels + 1) sum over l >= 1 of h_l w_l,
+ *                4-byte aligned (checked; 0 for a 1 x 1 image, where workspace may be NULL).  The result does not depend on what it held.
+ *     Work: one launch per level up, one per level down; a thread owns one pixel of the written level and walks the channels.
+ *   All of them read nothing back, allocate nothing, use no atomics and launch fixed grids derived from the shapes: legal inside a stream capture, the
+ *   same bytes every run.  Offsets into the maps are 64-bit.
+ * ---------------------------------------------------------------------------------------- */
+#define ADA_INPAINT_CHUNK 1024         /* columns of a row staged per step of ada_nearest_valid_fwd's row pass */
+int ada_nearest_valid_workspace_bytes(int32_t batch, int32_t h, int32_t w, int64_t* bytes);
+int ada_nearest_valid_fwd(const uint8_t* valid, int32_t batch, int32_t h, int32_t w, int32_t* index, int32_t* dist2, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+int ada_fill_gather_fwd(const float* x, const uint8_t* valid, const int32_t* index, int32_t batch, int32_t channels, int32_t h, int32_t w, float empty,
+                        float* out, void* stream);
+int ada_push_pull_workspace_bytes(int32_t batch, int32_t channels, int32_t h, int32_t w, int64_t* bytes);
+int ada_push_pull_fwd(const float* x, const uint8_t* valid, int32_t batch, int32_t channels, int32_t h, int32_t w, float empty, float* out,
+                      void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Tiled inference for inputs larger than the network's native 518 x 518 (the reference squashes every
