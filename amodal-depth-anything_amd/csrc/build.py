@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)     # isa_guard.py lives next to this file: the package builds without the repository's tools/
-SOURCES = ["ada_api.hip", "ada_igemm.hip", "ada_attention.hip", "ada_elementwise.hip", "ada_pipeline.hip", "ada_eval.hip", "ada_tail.hip", "ada_image.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip", "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip", "ada_inpaint.hip"]
+SOURCES = ["ada_api.hip", "ada_igemm.hip", "ada_attention.hip", "ada_elementwise.hip", "ada_pipeline.hip", "ada_eval.hip", "ada_tail.hip", "ada_image.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip", "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip", "ada_inpaint.hip", "ada_guided.hip"]
 HEADERS = ["ada_common.h", "ada_scan.h", "ada_mesh_rule.h", "ada_igemm_pipe4.inc", os.path.join("..", "..", "include", "ada_hip.h")]
 ARCH = "gfx950"
 # ada_tail.hip: no SLP vectorisation.  Vectorised, the producers' interpolation becomes v_pk_mul_f32 / v_pk_fma_f32 on register pairs
@@ -37,9 +37,11 @@ ARCH = "gfx950"
 # and the inverse mode's a depth + b must not turn into FMAs.
 # ada_inpaint.hip: no contraction.  The push-pull fill is compared bit for bit with the float32 numpy restatement in tests/_inpaint_ref.py: the masked means
 # ((s00 + s01) + s10) + s11 and the interpolation ((9 a + 3 b) + 3 c) + d round every product and every sum on their own.
+# ada_guided.hip: no contraction.  The apply pass of the guided filter is compared bit for bit with the fp64 numpy restatement in tests/_guided_ref.py: the source
+# coordinate ((X + 0.5) * w) / W - 0.5, the bilinear weights and ((c0 I0 + c1 I1) + c2 I2) + c3 round every product, quotient and sum on their own.
 PER_FILE_FLAGS = {"ada_tail.hip": ["-fno-slp-vectorize"], "ada_igemm.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"], "ada_geometry.hip": ["-ffp-contract=off"],
                   "ada_edges.hip": ["-ffp-contract=off"], "ada_raster.hip": ["-ffp-contract=off"], "ada_adaptive.hip": ["-ffp-contract=off"],
-                  "ada_inpaint.hip": ["-ffp-contract=off"]}
+                  "ada_inpaint.hip": ["-ffp-contract=off"], "ada_guided.hip": ["-ffp-contract=off"]}
 # ada_igemm.hip joined in round 4: a by-reference lambda capture of the k-walk counters put them into scratch behind the loop's "memory"-clobbering
 # waits -- 12 bytes reloaded every k-step of every GEMM, silently, for most of a round.  No kernel of these files may use scratch or spill VGPRs.
 # ada_image.hip / ada_pipeline.hip hold no hand-managed loads: their kernels are single memory-bound passes, one thread per output pixel, where any
@@ -63,8 +65,10 @@ PER_FILE_FLAGS = {"ada_tail.hip": ["-fno-slp-vectorize"], "ada_igemm.hip": ["-fn
 # (a sorting network indexed at run time) would live in scratch.
 # ada_inpaint.hip: a thread owns one pixel; the row pass keeps its running minimum (a distance and a position) in two registers and reads the candidates from
 # LDS, the pyramid's four children and four parents are named scalars.  The level table of the push-pull fill is a host array, never a kernel's.
+# ada_guided.hip: a thread keeps the 5 or 14 fp64 window sums of its pixel, and the apply pass its four taps and four pixels, in arrays indexed by unrolled
+# constants; the window itself is a loop over memory (columns) or LDS (rows), never a per-thread array.
 NO_SCRATCH = {"ada_tail.hip", "ada_igemm.hip", "ada_image.hip", "ada_pipeline.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip",
-              "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip", "ada_inpaint.hip"}
+              "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip", "ada_inpaint.hip", "ada_guided.hip"}
 # Round 4: the wrong results above were root-caused (profiles/r04_a_tail_inflight_register_root_cause.txt) -- NOT a hardware hazard of packed
 # fp32 beside MFMAs (tools/ubench/pk_f32_beside_mfma.hip: 0 mismatches) but the compiler copying registers that the kernel's inline-asm
 # fetches were still writing: with SLP on, the allocator parks a source row in other registers with v_mov_b64 placed ABOVE the hand-counted

@@ -922,6 +922,51 @@ def push_pull(x, valid, out, empty=0.0, workspace=None):
     _check(load().ada_push_pull_fwd(x.data_ptr(), pv, B, C, h, w, float(empty), po, ws.data_ptr() if ws_bytes else None, ws_bytes, _stream()), "ada_push_pull_fwd")
 
 
+def guided_workspace_bytes(batch: int, h: int, w: int, channels: int) -> int:
+    """Bytes of workspace ada_guided_coeff_fwd asks for (ada_guided_workspace_bytes): the fp64 planes of the window sums and of the window fits."""
+    n = ctypes.c_int64(0)
+    _check(load().ada_guided_workspace_bytes(int(batch), int(h), int(w), int(channels), ctypes.byref(n)), "ada_guided_workspace_bytes")
+    return n.value
+
+
+def _guide4(who, guide, batch):
+    """(gh, gw, C, ADA_DT_* of the guide) of a non-empty contiguous uint8 / fp32 [B, gh, gw, C] device tensor."""
+    if not isinstance(guide, torch.Tensor) or guide.dtype not in (torch.float32, torch.uint8):
+        raise HipExtError(f"{who}: guide must be an fp32 or uint8 tensor, got {getattr(guide, 'dtype', type(guide).__name__)}")
+    if guide.dim() != 4 or guide.shape[0] != batch or not guide.is_contiguous() or guide.numel() == 0:
+        raise HipExtError(f"{who}: guide must be a non-empty contiguous [{batch}, gh, gw, C] tensor, got {tuple(guide.shape)}")
+    _dev(guide, "guide")
+    return guide.shape[1], guide.shape[2], guide.shape[3], DT_F32 if guide.dtype == torch.float32 else DT_U8
+
+
+def guided_coeff_fwd(p, guide, radius, eps, coeff, covered, valid=None, workspace=None):
+    """p fp32 [B, h, w] and guide uint8 / fp32 [B, gh, gw, C] -> coeff fp64 [B, h, w, C + 1] and covered uint8 [B, h, w]: the window-averaged linear fit
+    of p in the guide's samples (ada_guided_coeff_fwd; include/ada_hip.h, "Guided filter").  ``eps`` in raw guide units; ``valid``: uint8 [B, h, w] or
+    None; ``workspace``: at least guided_workspace_bytes(B, h, w, C) bytes, allocated when None."""
+    who = "guided_coeff_fwd"
+    B, h, w = _maps3(who, p, "p")
+    gh, gw, C, dt = _guide4(who, guide, B)
+    pv = _like(who, "valid", valid, p, torch.uint8, optional=True)
+    pc = _sized(who, "coeff", coeff, (B, h, w, C + 1), torch.float64)
+    pm = _like(who, "covered", covered, p, torch.uint8)
+    _same_device(who, "p", p, guide=guide, coeff=coeff)
+    ws, ws_bytes = _bytes_of(who, workspace, guided_workspace_bytes(B, h, w, C), p.device)
+    _check(load().ada_guided_coeff_fwd(p.data_ptr(), pv, guide.data_ptr(), dt, B, h, w, gh, gw, C, int(radius), float(eps), pc, pm, ws.data_ptr(), ws_bytes,
+                                       _stream()), "ada_guided_coeff_fwd")
+
+
+def guided_apply_fwd(coeff, covered, guide, out, fill=float("nan")):
+    """coeff fp64 [B, h, w, C + 1], covered uint8 [B, h, w] and guide uint8 / fp32 [B, H, W, C] -> out fp32 [B, H, W]: the bilinearly interpolated
+    coefficients applied to the guide, ``fill`` where no covered tap has weight (ada_guided_apply_fwd)."""
+    who = "guided_apply_fwd"
+    B, h, w = _maps3(who, covered, "covered", torch.uint8)
+    H, W, C, dt = _guide4(who, guide, B)
+    pc = _sized(who, "coeff", coeff, (B, h, w, C + 1), torch.float64)
+    po = _sized(who, "out", out, (B, H, W), torch.float32)
+    _same_device(who, "covered", covered, guide=guide, coeff=coeff, out=out)
+    _check(load().ada_guided_apply_fwd(pc, covered.data_ptr(), guide.data_ptr(), dt, B, h, w, H, W, C, float(fill), po, _stream()), "ada_guided_apply_fwd")
+
+
 # --- tuning / diagnostic hooks (include/ada_hip.h, last section) ---------------------------------
 TILE_NAMES = {0: "256x32", 1: "128x64", 2: "256x128", 3: "256x256", 4: "128x128"}
 

@@ -74,6 +74,10 @@ FILTER_TILE_W, FILTER_TILE_H = 64, 4
 FILTER_COL_TILE_H = 16
 # ada_nearest_valid_fwd: columns of a row staged per step of the row pass
 INPAINT_CHUNK = 1024
+# ada_guided_coeff_fwd / ada_guided_apply_fwd: the radius cap, outputs of a row per workgroup of the row passes, pixels per thread of the apply pass
+GUIDED_MAX_RADIUS = 31
+GUIDED_TILE_W = 256
+GUIDED_APPLY_PX = 4
 
 
 class IgemmArgs(ctypes.Structure):
@@ -193,6 +197,10 @@ PROTOTYPES = {
     "ada_debug_set_timestamps": (None, [c_void_p]),
     "ada_debug_set_attention_variant": (None, [c_int]),
     "ada_debug_count_saturated": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "ada_guided_workspace_bytes": (c_int, [c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "ada_guided_coeff_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_double, c_void_p,
+                                     c_void_p, c_void_p, c_int64, c_void_p]),
+    "ada_guided_apply_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p]),
 }
 EXPORTS = tuple(PROTOTYPES)
 

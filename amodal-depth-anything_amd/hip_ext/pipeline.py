@@ -76,7 +76,8 @@ def fit_scale_shift(amodal: torch.Tensor, base: torch.Tensor, visible: torch.Ten
 
 @torch.no_grad()
 def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None, size: int = 518, out_size=None, check: bool = True,
-                       render: bool = False, min_area=None, min_area_connectivity: int = 4, render_percentiles=None, close=None):
+                       render: bool = False, min_area=None, min_area_connectivity: int = 4, render_percentiles=None, close=None, *,
+                       upsample: str = "nearest", guided_radius: int = 8, guided_eps: float = 1e-3):
     """The reference's infer.py call on the device: a decoded uint8 BGR(A) photo [h, w, 3 | 4] and K amodal masks (uint8 / bool [h, w] or
     [K, h, w]) in, an AmodalResult out.  The base network runs once (B = 1), the amodal network once as a batch of K.
 
@@ -95,13 +96,30 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
     hip_ext.quantile.percentile_range, taken on the device) instead of between 0 and 1.  None: the pictures are exactly the ones without it.
     close: when given, the AMODAL masks are closed by a close x close square (hip_ext.masks.closing, the MORPH_CLOSE of app.py:211), at their own
     resolution, after the min_area step -- a segmenter's pinholes and hairline gaps would otherwise be guidance for the network and keep the base depth
-    in the paste.  None: nothing runs, the call is exactly the one without it."""
+    in the paste.  None: nothing runs, the call is exactly the one without it.
+    upsample: how base and blended reach out_size.  "nearest" (the default) is the rule above, bit for bit the call without the keyword.  "guided"
+    takes ``base`` there with the photo as guide (hip_ext.guided.guided_upsample, radius guided_radius at the network size, guided_eps in [0, 1]^2
+    units): its depth edges lie where the photo's edges lie and not on the staircase of the nearest rule.  out_size must then be "image" or the photo's
+    own size, and the photo at least the network's size.  ``blended`` takes the guided base OUTSIDE the nearest-resized amodal mask and keeps the
+    nearest-resized blended values INSIDE it: a hidden surface has no edges in the photo, so the photo must not guide it.  The pictures of render=True
+    are not affected.  Without an out_size nothing is resized and the keyword changes nothing."""
     from ._staging import as_int
     from .image import _check_size, masks_to_tensor, photo_to_inputs, render_depth, resize_nearest
     size = _check_size(size, "amodal_infer_image")
     if not (out_size is None or (isinstance(out_size, str) and out_size == "image")
             or (isinstance(out_size, (tuple, list)) and len(out_size) == 2 and all((as_int(v) or 0) > 0 for v in out_size))):
         raise ValueError(f"amodal_infer_image: out_size must be None, 'image' or (h, w), got {out_size!r}")
+    if upsample not in ("nearest", "guided"):
+        raise ValueError(f"amodal_infer_image: upsample must be 'nearest' or 'guided', got {upsample!r}")
+    guided = upsample == "guided" and out_size is not None
+    if guided:
+        from .guided import _eps, _radius
+        _radius("amodal_infer_image", guided_radius), _eps("amodal_infer_image", guided_eps, torch.empty(0, dtype=torch.uint8))
+        photo = tuple(getattr(image, "shape", ()))[:2]
+        if out_size != "image" and tuple(as_int(v) for v in out_size) != photo:
+            raise ValueError(f"amodal_infer_image: upsample='guided' takes the photo as guide: out_size must be 'image' or the photo's size {photo}, got {out_size!r}")
+        if len(photo) == 2 and min(photo) < size:
+            raise ValueError(f"amodal_infer_image: upsample='guided' needs a photo at least as large as the network size {size}, got {photo}")
     device = next(amodal_model.parameters()).device
     rgb_raw, rgb, (h, w) = photo_to_inputs(image, size, device)
     if min_area is not None:
@@ -141,7 +159,12 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
         elif render:
             raw_rendered = render_depth(base_norm, out_size=target)
             amodal_rendered = render_depth(blended, m, out_size=target)
-        if target is not None:
+        if guided:
+            from .guided import guided_upsample
+            base_out = guided_upsample(base_norm, image[None, ..., :3], guided_radius, guided_eps, device=device)
+            inside = resize_nearest(m.contiguous(), *target) > 0
+            blended = torch.where(inside, resize_nearest(blended, *target), base_out)
+        elif target is not None:
             base_out, blended = resize_nearest(base_norm, *target), resize_nearest(blended, *target)
     if check and scale_shift is not None and not bool(torch.isfinite(scale_shift.cpu()).all()):
         raise ValueError("Denominator in slope calculation is zero.")

@@ -3,9 +3,9 @@
 
     python -m src.scripts.depth_to_view DEPTH OUT.png [--mask MASK.png] [--inverse NEAR FAR] [--max_ratio R] [--fov 55] [--image PHOTO]
                                                      [--yaw D] [--pitch D] [--shift X Y Z] [--size H W] [--max_error E] [--median K]
-                                                     [--fill_holes {nearest,smooth}]
+                                                     [--fill_holes {nearest,smooth}] [--guided R EPS]
 
-DEPTH, ``--mask``, ``--inverse``, ``--max_ratio``, ``--max_error``, ``--median`` and ``--image`` are read as ``src.scripts.depth_to_mesh`` reads them.  The camera orbits by
+DEPTH, ``--mask``, ``--inverse``, ``--max_ratio``, ``--max_error``, ``--median``, ``--guided`` and ``--image`` are read as ``src.scripts.depth_to_mesh`` reads them.  The camera orbits by
 ``--yaw`` / ``--pitch`` degrees about the point on the optical axis at the map's median depth and then moves by ``--shift``
 (hip_ext.geometry.look_at_pose).  With ``--image`` the output is the photo-coloured view; without it, the view's depth through the colour map of
 hip_ext.image.colorize over the inverse depth (holes and background in its background grey).  ``--size`` renders at another size than the map's, with the same field
@@ -25,7 +25,7 @@ if _PKG not in sys.path:
     sys.path.insert(0, _PKG)
 
 from hip_ext import geometry  # noqa: E402
-from src.scripts.depth_to_mesh import read_depth, read_mask  # noqa: E402
+from src.scripts.depth_to_mesh import guided_depth, read_depth, read_mask, read_photo  # noqa: E402
 
 INVALID = -99.0      # colorize's marker of a pixel without a value: the view's background and holes
 
@@ -53,20 +53,22 @@ def pivot_depth(depth, ab=None) -> float:
 
 
 def view_file(src, dst, mask=None, inverse=None, max_ratio=None, fov=55.0, image=None, yaw=0.0, pitch=0.0, shift=(0.0, 0.0, 0.0), size=None,
-              device="cuda", max_error=None, median=None, fill_holes=None):
+              device="cuda", max_error=None, median=None, fill_holes=None, guided=None):
     """Renders one file; returns the uint8 picture [H, W, 3] (R, G, B) that was written."""
     from hip_ext import image as hip_image
+    if guided is not None and image is None:
+        raise ValueError("--guided needs --image: the photo is the guide")
     ab = inverse_pair(inverse)
     depth = read_depth(src, normalise=ab is not None)
-    colors = None
-    if image is not None:
-        colors = np.ascontiguousarray(np.asarray(Image.open(image).convert("RGB")))
-        if colors.shape[:2] != depth.shape:
-            raise ValueError(f"{image}: photo of shape {colors.shape[:2]} for a depth map of shape {depth.shape}")
-    h, w = depth.shape if size is None else (int(size[0]), int(size[1]))
-    mesh = geometry.depth_to_mesh(depth, mask=None if mask is None else read_mask(mask, depth.shape), colors=colors, fov_deg=fov, inverse=ab,
+    colors = None if image is None else read_photo(image, depth.shape, guided)
+    mask = None if mask is None else read_mask(mask, depth.shape)
+    pivot = pivot_depth(depth, ab)      # from the file that was read: the guided depth stays on the device
+    if guided is not None:
+        depth, mask = guided_depth(depth, mask, colors, guided, device)
+    h, w = tuple(depth.shape) if size is None else (int(size[0]), int(size[1]))
+    mesh = geometry.depth_to_mesh(depth, mask=mask, colors=colors, fov_deg=fov, inverse=ab,
                                   max_ratio=max_ratio, max_error=max_error, median=median, device=device)
-    R, t = geometry.look_at_pose(yaw, pitch, shift, pivot_z=pivot_depth(depth, ab))
+    R, t = geometry.look_at_pose(yaw, pitch, shift, pivot_z=pivot)
     view = geometry.render_mesh(mesh, h, w, fov_deg=fov, R=R, t=t, out="w", fill=INVALID, device=device)
     if fill_holes is not None:
         view = geometry.fill_view(view, fill_holes)
@@ -95,6 +97,7 @@ def build_parser():
     ap.add_argument("--max_error", type=float, default=None, help="adaptive mesh: the largest relative disparity error of a triangle that is not split (default: two triangles per cell)")
     ap.add_argument("--median", type=int, default=None, metavar="K", help="median-filter the depth over K x K windows (K odd) among the samples inside the mask before meshing: removes the flying pixels of occlusion borders")
     ap.add_argument("--fill_holes", choices=("nearest", "smooth"), default=None, help="fill the pixels no triangle covered from the covered ones: the nearest covered pixel's value, or the smooth push-pull fill (default: they keep the background)")
+    ap.add_argument("--guided", type=float, nargs=2, metavar=("R", "EPS"), default=None, help="guided filter of the depth with --image as guide, radius R (integer) and eps EPS in [0, 1]^2 units; a photo larger than the depth map up-samples the depth to its size")
     ap.add_argument("--device", default="cuda")
     return ap
 
@@ -102,7 +105,7 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
     picture = view_file(args.input, args.output, args.mask, args.inverse, args.max_ratio, args.fov, args.image, args.yaw, args.pitch, tuple(args.shift),
-                        args.size, args.device, args.max_error, args.median, args.fill_holes)
+                        args.size, args.device, args.max_error, args.median, args.fill_holes, args.guided)
     print(f"{args.output}: {picture.shape[0]} x {picture.shape[1]}")
     return 0
 

@@ -1023,6 +1023,51 @@ void ada_debug_set_attention_variant(int v);
  * activation buffers after a forward (hip_ext.engine.DepthEngine.saturation_report).  Asynchronous on `stream`; not on the hot path. */
 int ada_debug_count_saturated(const void* buf, int64_t n, void* count, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Guided filter (He, Sun, Tang) and its fast form, guided joint up-sampling (additions under ABI 10): a map is fitted, window by window, as a linear
+ * function of a guide image, and the fit is applied to the guide -- smoothing that keeps the guide's edges, and the way from depth at the network's size
+ * to depth at the photo's size.  The reference has no such operation: it resizes with cv2's nearest rule (infer.py:77, 113).
+ *   INPUT.  p: fp32 [batch][h][w] packed.  valid: optional uint8 of that shape (NULL: every sample).  A sample VOTES when valid is absent or non-zero
+ *     there and p is not NaN; what lies under a sample that does not vote never reaches a result.  guide I: uint8 (ADA_DT_U8) or fp32 (ADA_DT_F32)
+ *     [batch][gh][gw][channels] packed, channels C = 1 or 3, gh >= h and gw >= w.  radius r, 0 <= r <= ADA_GUIDED_MAX_RADIUS: the window of a pixel
+ *     is the (2 r + 1)^2 positions around it that lie inside the image -- there is no other border rule.  eps > 0 and finite, in raw guide units
+ *     (eps 255^2 for a uint8 guide and an eps meant for [0, 1]).  Sides <= 32767 (else ADA_EUNSUPPORTED), batch <= 65535.
+ *   COEFFICIENT PASS, at the map's size (ada_guided_coeff_fwd).  The guide sample of map pixel (y, x) is I[((2 y + 1) gh) / (2 h)][((2 x + 1) gw) / (2 w)]
+ *     (integer quotients): the identity for equal sizes, plain sub-sampling otherwise.  Over the n voting samples of a pixel's window, from the sums
+ *     S1 = n, SI, SII = sum I I^T, Sp, SIp:  mI = SI / n, mp = Sp / n, Cov(I, I) = SII / n - mI mI^T, Cov(I, p) = SIp / n - mI mp,
+ *         a = (Cov(I, I) + eps U)^-1 Cov(I, p)      (C = 1: a quotient; C = 3: an L D L^T solve, never the adjugate),      b = mp - a . mI.
+ *     A window with n = 0 has no (a, b).  coeff fp64 [batch][h][w][C + 1] = (mean a_0 .. mean a_{C-1}, mean b) over the window's pixels that have one;
+ *     covered uint8 [batch][h][w] = 1 where at least one has, else 0 and coeff = 0.
+ *   APPLY PASS, at the guide's size H = gh, W = gw (ada_guided_apply_fwd).  Output pixel (Y, X) has the source coordinates
+ *         sy = ((Y + 0.5) * h) / H - 0.5 clamped to [0, h - 1],  sx = ((X + 0.5) * w) / W - 0.5 clamped to [0, w - 1]      (fp64, in this order)
+ *     y0 = floor(sy), y1 = min(y0 + 1, h - 1), fy = sy - y0, likewise x0, x1, fx.  The taps, in this order, are (y0, x0), (y0, x1), (y1, x0), (y1, x1) with
+ *     the weights (1 - fy)(1 - fx), (1 - fy) fx, fy (1 - fx), fy fx.  A tap of weight 0 is never read (equal sizes give sy = Y exactly: the single tap).
+ *     A tap of positive weight CONTRIBUTES when covered there.  c_j = sum over the contributing taps, in order, of weight * coeff_j; when a tap of
+ *     positive weight does not contribute, c_j is divided by the sum (in order) of the contributing weights.  No contributing tap: out = fill.  Otherwise
+ *         out = fp32( ((c_0 I_0 + c_1 I_1) + c_2 I_2) + c_C )       (C = 1: c_0 I_0 + c_1)  with I the guide at (Y, X).
+ *   ARITHMETIC.  Every sum, product, quotient and the solve in fp64, each rounded on its own (csrc/ada_guided.hip is built without floating-point
+ *     contraction); one rounding to fp32 at the very end.  The order of a window's sums is the kernels' own (rows of a column, then columns): against an
+ *     fp64 restatement the fp32 results agree except at a rounding boundary.  The apply pass from given coeff / covered is reproduced bit for bit.
+ *   WORK.  Coefficients: four launches, a thread per map pixel -- the column sums of the 5 (C = 1) or 14 (C = 3) moment planes, their row sums (a row's
+ *     planes staged through LDS, ADA_GUIDED_TILE_W outputs per workgroup) with the solve, and the same two steps for the C + 2 planes (a, b, has).
+ *     workspace  workspace_bytes >= ada_guided_workspace_bytes = 8 batch h w (moment planes + C + 2), 8-byte aligned (checked).  The result does
+ *                not depend on what it held.
+ *     Apply: one launch, a thread per ADA_GUIDED_APPLY_PX pixels of a row; vector loads and stores when W is a multiple of that and guide and out
+ *     lie on 16-byte boundaries, the same values element by element otherwise.
+ *   Refusals (ADA_EINVAL before any launch): a null pointer, r out of range, eps not finite and positive, C not 1 or 3, a guide dtype other than the
+ *   two, a guide smaller than the map, a workspace that is too small.  All of them read nothing back, allocate nothing, use no atomics and launch fixed
+ *   grids derived from the shapes: legal inside a stream capture, the same bytes every run.  Offsets into the maps are 64-bit.
+ * ---------------------------------------------------------------------------------------- */
+#define ADA_GUIDED_MAX_RADIUS 31
+#define ADA_GUIDED_TILE_W 256          /* outputs of a row per workgroup of the row passes */
+#define ADA_GUIDED_APPLY_PX 4          /* pixels of a row per thread of the apply pass */
+int ada_guided_workspace_bytes(int32_t batch, int32_t h, int32_t w, int32_t channels, int64_t* bytes);
+int ada_guided_coeff_fwd(const float* p, const uint8_t* valid, const void* guide, int32_t guide_dtype, int32_t batch, int32_t h, int32_t w, int32_t gh,
+                         int32_t gw, int32_t channels, int32_t radius, double eps, double* coeff, uint8_t* covered, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+int ada_guided_apply_fwd(const double* coeff, const uint8_t* covered, const void* guide, int32_t guide_dtype, int32_t batch, int32_t h, int32_t w,
+                         int32_t gh, int32_t gw, int32_t channels, float fill, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
