@@ -15,7 +15,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)     # isa_guard.py lives next to this file: the package builds without the repository's tools/
-SOURCES = ["ada_api.hip", "ada_igemm.hip", "ada_attention.hip", "ada_elementwise.hip", "ada_pipeline.hip", "ada_eval.hip", "ada_tail.hip", "ada_image.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip", "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip", "ada_inpaint.hip", "ada_guided.hip"]
+SOURCES = ["ada_api.hip", "ada_igemm.hip", "ada_attention.hip", "ada_elementwise.hip", "ada_pipeline.hip", "ada_eval.hip", "ada_tail.hip", "ada_image.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip", "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip", "ada_inpaint.hip", "ada_guided.hip", "ada_membrane.hip"]
 HEADERS = ["ada_common.h", "ada_scan.h", "ada_mesh_rule.h", "ada_igemm_pipe4.inc", os.path.join("..", "..", "include", "ada_hip.h")]
 ARCH = "gfx950"
 # ada_tail.hip: no SLP vectorisation.  Vectorised, the producers' interpolation becomes v_pk_mul_f32 / v_pk_fma_f32 on register pairs
@@ -39,6 +39,8 @@ ARCH = "gfx950"
 # ((s00 + s01) + s10) + s11 and the interpolation ((9 a + 3 b) + 3 c) + d round every product and every sum on their own.
 # ada_guided.hip: no contraction.  The apply pass of the guided filter is compared bit for bit with the fp64 numpy restatement in tests/_guided_ref.py: the source
 # coordinate ((X + 0.5) * w) / W - 0.5, the bilinear weights and ((c0 I0 + c1 I1) + c2 I2) + c3 round every product, quotient and sum on their own.
+# ada_membrane.hip: contraction stays on.  Nothing of the conjugate-gradient solve is compared bit for bit with numpy (the tests bound its error by the
+# residual and the inverse's norm); the one product that two workgroups both form, the next direction in a tile and in its neighbours' halos, is an explicit fma.
 PER_FILE_FLAGS = {"ada_tail.hip": ["-fno-slp-vectorize"], "ada_igemm.hip": ["-fno-slp-vectorize", "-Wno-inline-asm"], "ada_geometry.hip": ["-ffp-contract=off"],
                   "ada_edges.hip": ["-ffp-contract=off"], "ada_raster.hip": ["-ffp-contract=off"], "ada_adaptive.hip": ["-ffp-contract=off"],
                   "ada_inpaint.hip": ["-ffp-contract=off"], "ada_guided.hip": ["-ffp-contract=off"]}
@@ -67,8 +69,10 @@ PER_FILE_FLAGS = {"ada_tail.hip": ["-fno-slp-vectorize"], "ada_igemm.hip": ["-fn
 # LDS, the pyramid's four children and four parents are named scalars.  The level table of the push-pull fill is a host array, never a kernel's.
 # ada_guided.hip: a thread keeps the 5 or 14 fp64 window sums of its pixel, and the apply pass its four taps and four pixels, in arrays indexed by unrolled
 # constants; the window itself is a loop over memory (columns) or LDS (rows), never a per-thread array.
+# ada_membrane.hip: a thread owns four pixels of a column and walks them with a counted loop over memory; the halo tile of the direction and the
+# reduction trees live in LDS, the per-plane scalars arrive as one 24-byte struct load.  A per-thread array of the four pixels would be indexed at run time.
 NO_SCRATCH = {"ada_tail.hip", "ada_igemm.hip", "ada_image.hip", "ada_pipeline.hip", "ada_protocol_eval.hip", "ada_label.hip", "ada_ladder.hip", "ada_masks.hip", "ada_quantile.hip", "ada_geometry.hip",
-              "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip", "ada_inpaint.hip", "ada_guided.hip"}
+              "ada_edges.hip", "ada_raster.hip", "ada_adaptive.hip", "ada_filters.hip", "ada_inpaint.hip", "ada_guided.hip", "ada_membrane.hip"}
 # Round 4: the wrong results above were root-caused (profiles/r04_a_tail_inflight_register_root_cause.txt) -- NOT a hardware hazard of packed
 # fp32 beside MFMAs (tools/ubench/pk_f32_beside_mfma.hip: 0 mismatches) but the compiler copying registers that the kernel's inline-asm
 # fetches were still writing: with SLP on, the allocator parks a source row in other registers with v_mov_b64 placed ABOVE the hand-counted

@@ -967,6 +967,65 @@ def guided_apply_fwd(coeff, covered, guide, out, fill=float("nan")):
     _check(load().ada_guided_apply_fwd(pc, covered.data_ptr(), guide.data_ptr(), dt, B, h, w, H, W, C, float(fill), po, _stream()), "ada_guided_apply_fwd")
 
 
+def membrane_workspace_bytes(batch: int, channels: int, h: int, w: int) -> int:
+    """Bytes of workspace the ada_membrane_*_fwd calls of one solve share (ada_membrane_workspace_bytes): the fp64 state of conjugate gradients."""
+    n = ctypes.c_int64(0)
+    _check(load().ada_membrane_workspace_bytes(int(batch), int(channels), int(h), int(w), ctypes.byref(n)), "ada_membrane_workspace_bytes")
+    return n.value
+
+
+def _membrane_workspace(who, workspace, x):
+    B, C, h, w = _planes4(who, x)
+    ws, ws_bytes = _bytes_of(who, workspace, membrane_workspace_bytes(B, C, h, w), x.device)
+    return B, C, h, w, ws, ws_bytes
+
+
+def membrane_begin(x, known, workspace, domain=None, guess=None, minus=None, tol=1e-9):
+    """Starts a membrane solve (ada_membrane_begin_fwd; include/ada_hip.h, "Membrane solve"): x fp32 [B, C, h, w], known and the optional domain uint8
+    [B, h, w]; ``guess`` (fp32 like x, None: 0) is the start on the unknown pixels; with ``minus`` (fp32 like x) the data on a known pixel is x - minus in
+    fp64.  ``workspace``: a contiguous device tensor of at least membrane_workspace_bytes(B, C, h, w) bytes, which carries the solve to membrane_end."""
+    who = "membrane_begin"
+    if workspace is None:
+        raise HipExtError(f"{who}: the workspace carries the solve from call to call and cannot be None")
+    B, C, h, w, ws, ws_bytes = _membrane_workspace(who, workspace, x)
+    pk = _sized(who, "known", known, (B, h, w), torch.uint8)
+    pd = None if domain is None else _sized(who, "domain", domain, (B, h, w), torch.uint8)
+    pg, pm = _like(who, "guess", guess, x, torch.float32, optional=True), _like(who, "minus", minus, x, torch.float32, optional=True)
+    _same_device(who, "x", x, known=known, domain=domain)
+    _check(load().ada_membrane_begin_fwd(x.data_ptr(), pm, pk, pd, pg, B, C, h, w, float(tol), ws.data_ptr(), ws_bytes, _stream()), "ada_membrane_begin_fwd")
+
+
+def membrane_iterate(x, workspace, iterations, frozen=None):
+    """Exactly ``iterations`` conjugate-gradient steps of the solve in ``workspace`` for all planes of x's shape, frozen planes idle
+    (ada_membrane_iterate_fwd).  ``frozen``: optional uint8 [B * C] that receives the planes' frozen flags."""
+    who = "membrane_iterate"
+    if workspace is None:
+        raise HipExtError(f"{who}: the workspace carries the solve from call to call and cannot be None")
+    B, C, h, w, ws, ws_bytes = _membrane_workspace(who, workspace, x)
+    pf = None if frozen is None else _sized(who, "frozen", frozen, (B * C,), torch.uint8)
+    _same_device(who, "x", x, frozen=frozen)
+    _check(load().ada_membrane_iterate_fwd(B, C, h, w, int(iterations), pf, ws.data_ptr(), ws_bytes, _stream()), "ada_membrane_iterate_fwd")
+
+
+def membrane_end(x, workspace, residual, iterations, converged, out=None, out64=None, plus=None):
+    """Finishes the solve in ``workspace`` (ada_membrane_end_fwd): out fp32 and / or out64 fp64 [B, C, h, w] = the solution on the unknown pixels (plus
+    ``plus``, fp32 like x, when given) and x bit for bit elsewhere; per plane residual fp64 [B * C] (the true residual's max norm), iterations int32 and
+    converged uint8."""
+    who = "membrane_end"
+    if workspace is None:
+        raise HipExtError(f"{who}: the workspace carries the solve from call to call and cannot be None")
+    B, C, h, w, ws, ws_bytes = _membrane_workspace(who, workspace, x)
+    if out is None and out64 is None:
+        raise HipExtError(f"{who}: out and out64 are both None")
+    po, po64 = _like(who, "out", out, x, torch.float32, optional=True), _like(who, "out64", out64, x, torch.float64, optional=True)
+    pp = _like(who, "plus", plus, x, torch.float32, optional=True)
+    pr = _sized(who, "residual", residual, (B * C,), torch.float64)
+    pi = _sized(who, "iterations", iterations, (B * C,), torch.int32)
+    pc = _sized(who, "converged", converged, (B * C,), torch.uint8)
+    _same_device(who, "x", x, residual=residual, iterations=iterations, converged=converged)
+    _check(load().ada_membrane_end_fwd(x.data_ptr(), pp, B, C, h, w, po, po64, pr, pi, pc, ws.data_ptr(), ws_bytes, _stream()), "ada_membrane_end_fwd")
+
+
 # --- tuning / diagnostic hooks (include/ada_hip.h, last section) ---------------------------------
 TILE_NAMES = {0: "256x32", 1: "128x64", 2: "256x128", 3: "256x256", 4: "128x128"}
 

@@ -74,6 +74,9 @@ FILTER_TILE_W, FILTER_TILE_H = 64, 4
 FILTER_COL_TILE_H = 16
 # ada_nearest_valid_fwd: columns of a row staged per step of the row pass
 INPAINT_CHUNK = 1024
+# ada_membrane_*_fwd: a workgroup's tile, which is also the partition of every reduction (one partial sum per tile and plane)
+MEMBRANE_TILE_H = 16
+MEMBRANE_TILE_W = 64
 # ada_guided_coeff_fwd / ada_guided_apply_fwd: the radius cap, outputs of a row per workgroup of the row passes, pixels per thread of the apply pass
 GUIDED_MAX_RADIUS = 31
 GUIDED_TILE_W = 256
@@ -188,6 +191,11 @@ PROTOTYPES = {
     "ada_fill_gather_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p]),
     "ada_push_pull_workspace_bytes": (c_int, [c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
     "ada_push_pull_fwd": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ada_membrane_workspace_bytes": (c_int, [c_int32, c_int32, c_int32, c_int32, POINTER(c_int64)]),
+    "ada_membrane_begin_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_void_p, c_int64, c_void_p]),
+    "ada_membrane_iterate_fwd": (c_int, [c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ada_membrane_end_fwd": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                     c_void_p]),
     "ada_tile_blend_fwd": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "ada_selftest": (c_int, [c_void_p, c_int64, c_void_p]),
     "ada_debug_set_tile": (None, [c_int]),

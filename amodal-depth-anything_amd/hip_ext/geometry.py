@@ -538,20 +538,20 @@ def render_layers(layers, h, w, objects=None, scene=True, near=1.0, far=10.0, ou
     return _render(who, [(m.points, m.triangles, m.colors) for m in meshes], labels, h, w, K, fov_deg, R, t, out, inverse, fill, fill_color, device)
 
 
-_FILLS = ("smooth", "nearest")
+_FILLS = ("smooth", "nearest", "harmonic")
 
 
 def _fill_fn(who, method):
     if method not in _FILLS:
-        raise ValueError(f"{who}: method must be 'smooth' or 'nearest', got {method!r}")
-    return _inpaint.fill_smooth if method == "smooth" else _inpaint.fill_nearest
+        raise ValueError(f"{who}: method must be 'smooth', 'nearest' or 'harmonic', got {method!r}")
+    return {"smooth": _inpaint.fill_smooth, "nearest": _inpaint.fill_nearest, "harmonic": _inpaint.fill_harmonic}[method]
 
 
 @torch.no_grad()
 def fill_view(view, method="smooth") -> View:
     """The view with its holes filled: the pixels no triangle covered (``view.owner < 0``) get depth, and colour where ``view.color`` is not None, from
     the pixels a triangle covered -- hip_ext.inpaint.fill_smooth (``method='smooth'``, the push-pull fill) or fill_nearest (``'nearest'``, the value of
-    the nearest covered pixel).  Covered pixels keep their bits; ``index`` and ``owner`` are returned unchanged, so the caller still sees which pixels
+    the nearest covered pixel) or fill_harmonic (``'harmonic'``, the membrane solve: every hole pixel the mean of its neighbours).  Covered pixels keep their bits; ``index`` and ``owner`` are returned unchanged, so the caller still sees which pixels
     were holes.  A view without any covered pixel comes back unchanged.  The fill interpolates what is seen and knows nothing of the geometry behind a
     hole.  Nothing is read back: the empty view is kept by a select on the device."""
     who = "fill_view"
@@ -569,7 +569,7 @@ def fill_view(view, method="smooth") -> View:
 def remove_objects(depth, masks, image=None, grow=1, method="smooth", device=None):
     """(depth_filled, image_filled or None): the depth map, and the photo when given, with the objects under ``masks`` taken out.  The union of ``masks``
     (uint8 / bool [K, h, w] or [h, w], non-zero = object) is dilated ``grow`` times with hip_ext.masks.dilate(size=3) (``grow=0``: not at all), marked
-    invalid and filled from the rest with hip_ext.inpaint.fill_smooth / fill_nearest (``method``).  Pixels outside the grown union keep their bits.
+    invalid and filled from the rest with hip_ext.inpaint.fill_smooth / fill_nearest / fill_harmonic (``method``).  Pixels outside the grown union keep their bits.
     ``depth``: fp32 [h, w]; ``image``: uint8 [h, w, 3] or None.  Through depth_to_mesh the result is a background layer to render behind amodal_layers'
     objects.  This is geometry-blind interpolation of the surroundings, not a learned completion: what stood behind the objects is not recovered."""
     who = "remove_objects"

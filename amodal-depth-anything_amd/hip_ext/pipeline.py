@@ -77,7 +77,8 @@ def fit_scale_shift(amodal: torch.Tensor, base: torch.Tensor, visible: torch.Ten
 @torch.no_grad()
 def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None, size: int = 518, out_size=None, check: bool = True,
                        render: bool = False, min_area=None, min_area_connectivity: int = 4, render_percentiles=None, close=None, *,
-                       upsample: str = "nearest", guided_radius: int = 8, guided_eps: float = 1e-3):
+                       blend: str = "paste", seam_tol: float = 1e-9, seam_max_iter=None, upsample: str = "nearest", guided_radius: int = 8,
+                       guided_eps: float = 1e-3):
     """The reference's infer.py call on the device: a decoded uint8 BGR(A) photo [h, w, 3 | 4] and K amodal masks (uint8 / bool [h, w] or
     [K, h, w]) in, an AmodalResult out.  The base network runs once (B = 1), the amodal network once as a batch of K.
 
@@ -102,7 +103,13 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
     units): its depth edges lie where the photo's edges lie and not on the staircase of the nearest rule.  out_size must then be "image" or the photo's
     own size, and the photo at least the network's size.  ``blended`` takes the guided base OUTSIDE the nearest-resized amodal mask and keeps the
     nearest-resized blended values INSIDE it: a hidden surface has no edges in the photo, so the photo must not guide it.  The pictures of render=True
-    are not affected.  Without an out_size nothing is resized and the keyword changes nothing."""
+    are not affected.  Without an out_size nothing is resized and the keyword changes nothing.
+    blend: how the prediction enters ``blended``.  "paste" (the default) is the paste and border blur above, bit for bit the call without the keyword.
+    "seamless" needs visible_masks and adds a spatially varying correction instead of a seam: per object, with pred' = pred * scale + shift, the
+    difference base - pred' on the object's visible part (visible and inside the amodal mask) is extended harmonically under the occluder, over the amodal
+    mask and no further (hip_ext.inpaint's membrane solve, fp64, stopped at seam_tol / seam_max_iter as fill_harmonic's tol / max_iter), and
+    blended = pred' + correction inside the mask, base bit for bit on the visible part and outside the mask; there is no border blur.  A part of the mask
+    that no visible pixel reaches keeps the plain paste.  scale_shift, check, render, out_size and upsample act on the new ``blended`` as before."""
     from ._staging import as_int
     from .image import _check_size, masks_to_tensor, photo_to_inputs, render_depth, resize_nearest
     size = _check_size(size, "amodal_infer_image")
@@ -111,6 +118,14 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
         raise ValueError(f"amodal_infer_image: out_size must be None, 'image' or (h, w), got {out_size!r}")
     if upsample not in ("nearest", "guided"):
         raise ValueError(f"amodal_infer_image: upsample must be 'nearest' or 'guided', got {upsample!r}")
+    if blend not in ("paste", "seamless"):
+        raise ValueError(f"amodal_infer_image: blend must be 'paste' or 'seamless', got {blend!r}")
+    if blend == "seamless":
+        from .inpaint import _check_solver
+        if visible_masks is None:
+            raise ValueError("amodal_infer_image: blend='seamless' needs visible_masks: the correction is pinned to each object's visible part (pinning it "
+                             "to the pixels outside the amodal mask would tie the object to its occluders)")
+        seam_tol, seam_max_iter, _ = _check_solver("amodal_infer_image", seam_tol, seam_max_iter, None, "smooth")
     guided = upsample == "guided" and out_size is not None
     if guided:
         from .guided import _eps, _radius
@@ -147,8 +162,17 @@ def amodal_infer_image(model_raw, amodal_model, image, masks, visible_masks=None
         base_k = base_norm.expand(K, -1, -1).contiguous()
         m = mask01.reshape(K, S, S)
         scale_shift = fit_scale_shift(pred, base_k, visible.reshape(K, S, S)) if visible is not None else None
-        blended = torch.empty_like(pred)
-        blend_ex(pred, base_k, m, blended, scale_shift)
+        if blend == "seamless":
+            from .inpaint import _membrane
+            aligned = pred * scale_shift[:, 0, None, None] + scale_shift[:, 1, None, None]      # fp32, product and sum rounded on their own, as ada_blend_ex
+            inside = m > 0
+            known = (visible.reshape(K, S, S) > 0) & inside
+            every = None if torch.cuda.is_current_stream_capturing() else 64      # outside a capture: stop issuing steps once every object is done
+            blended = _membrane("amodal_infer_image", base_k[:, None], known, inside, aligned[:, None].contiguous(), 0.0, seam_tol, seam_max_iter, every,
+                                "smooth")[0][:, 0].contiguous()
+        else:
+            blended = torch.empty_like(pred)
+            blend_ex(pred, base_k, m, blended, scale_shift)
         base_out = base_norm
         target = None if out_size is None else ((h, w) if out_size == "image" else tuple(out_size))
         if render and render_percentiles is not None:

@@ -3,7 +3,7 @@
 
     python -m src.scripts.depth_to_view DEPTH OUT.png [--mask MASK.png] [--inverse NEAR FAR] [--max_ratio R] [--fov 55] [--image PHOTO]
                                                      [--yaw D] [--pitch D] [--shift X Y Z] [--size H W] [--max_error E] [--median K]
-                                                     [--fill_holes {nearest,smooth}] [--guided R EPS]
+                                                     [--fill_holes {nearest,smooth,harmonic}] [--guided R EPS]
 
 DEPTH, ``--mask``, ``--inverse``, ``--max_ratio``, ``--max_error``, ``--median``, ``--guided`` and ``--image`` are read as ``src.scripts.depth_to_mesh`` reads them.  The camera orbits by
 ``--yaw`` / ``--pitch`` degrees about the point on the optical axis at the map's median depth and then moves by ``--shift``
@@ -96,7 +96,7 @@ def build_parser():
     ap.add_argument("--size", type=int, nargs=2, metavar=("H", "W"), default=None, help="target size (default: the depth map's)")
     ap.add_argument("--max_error", type=float, default=None, help="adaptive mesh: the largest relative disparity error of a triangle that is not split (default: two triangles per cell)")
     ap.add_argument("--median", type=int, default=None, metavar="K", help="median-filter the depth over K x K windows (K odd) among the samples inside the mask before meshing: removes the flying pixels of occlusion borders")
-    ap.add_argument("--fill_holes", choices=("nearest", "smooth"), default=None, help="fill the pixels no triangle covered from the covered ones: the nearest covered pixel's value, or the smooth push-pull fill (default: they keep the background)")
+    ap.add_argument("--fill_holes", choices=("nearest", "smooth", "harmonic"), default=None, help="fill the pixels no triangle covered from the covered ones: the nearest covered pixel's value, the smooth push-pull fill, or the harmonic fill of the membrane solve (default: they keep the background)")
     ap.add_argument("--guided", type=float, nargs=2, metavar=("R", "EPS"), default=None, help="guided filter of the depth with --image as guide, radius R (integer) and eps EPS in [0, 1]^2 units; a photo larger than the depth map up-samples the depth to its size")
     ap.add_argument("--device", default="cuda")
     return ap

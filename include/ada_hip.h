@@ -975,6 +975,52 @@ int ada_push_pull_fwd(const float* x, const uint8_t* valid, int32_t batch, int32
                       void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Membrane solve: the discrete harmonic extension of the known pixels of a map over a masked grid (additions under ABI 10).  The exact counterpart of
+ * ada_push_pull_fwd, and with a source added back (minus / plus below) seamless cloning in its membrane form.  The reference has no such operation.
+ *   PROBLEM.  Grid h x w, 4-neighbour graph, per image: domain (uint8 [batch][h][w], non-zero = the pixel is a node; NULL = every pixel) and known (uint8,
+ *     non-zero = Dirichlet pixel; it counts only inside domain).  x fp32 [batch][channels][h][w] packed, one mask pair for the channels of an image.  The
+ *     unknowns are U = domain and not known.  For every p in U
+ *         sum over q in N4(p), q inside the image, q in domain, of (u_p - u_q) = 0,      u_q = d_q on a known q,
+ *     with the data d = x, or d = x - minus (both widened to fp64 first) when minus is given.  An edge to a pixel outside the image or outside domain does
+ *     not exist (natural boundary).  The matrix is a symmetric M-matrix, positive definite on every 4-connected component of domain that holds a known
+ *     pixel.  A component without one is a pure Neumann problem with a zero right side: conjugate gradients leave it at the mean of its start values, and
+ *     callers overwrite it (hip_ext.inpaint does, with ``empty``) or keep it out of domain.
+ *   OUTPUT.  On U: u_p, or u_p + plus_p when plus is given, rounded to fp32 once (out) and / or as fp64 (out64).  On every other pixel, known pixels and
+ *     pixels outside domain alike: x bit for bit, moved as a 32-bit word (out64: that float widened).  The value under a pixel that is not known, NaN and
+ *     inf included, never reaches a result (selects).  minus and plus are read on known pixels and on U respectively, nowhere else.
+ *   METHOD.  Conjugate gradients in fp64.  Per plane the workspace holds u, r, q, two direction buffers, one code byte per pixel of the image, three
+ *     partial sums per tile and two slots of scalars (r.r, tol, frozen, steps).  A step is two launches of (tiles, channels, batch) workgroups, a
+ *     workgroup per ADA_MEMBRANE_TILE_H x ADA_MEMBRANE_TILE_W tile: the first reduces the tiles' r.r and max |r|, forms p' = r + beta p into the other
+ *     direction buffer, q = A p' and the tiles' p'.q; the second reduces p'.q and updates u, r and the partials.  Every workgroup reduces the partials
+ *     for itself in one fixed order; no float atomics, no grid-wide barrier, no cooperative launch, no workgroup that waits for another.  Every sum has
+ *     one order that depends on (h, w) alone: a plane's result is the same bytes from run to run, and alone or inside any batch.
+ *   FREEZE.  A plane is frozen once max |r| of the recurrence is <= tol, once p'.A p' <= 0, or once r.r or alpha is not finite.  From then on the kernels
+ *     leave its state as it is.  A NaN in a known pixel costs that plane its result (converged = 0) and nobody a hang: the launches are counted, not awaited.
+ *   ada_membrane_begin_fwd    writes the codes, the start vector (d on known pixels; guess, fp32, on U, or 0 when guess is NULL), the start residual and
+ *     the scalars.  tol >= 0 and finite, in the units of x.  Two launches.
+ *   ada_membrane_iterate_fwd  exactly ``iterations`` steps for all planes, frozen ones idle: 2 iterations launches, one more when ``frozen`` (uint8
+ *     [batch channels], optional) is given and receives the planes' flags.  begin -> iterate(a) -> iterate(b) -> end is begin -> iterate(a + b) -> end bit
+ *     for bit: the state is the workspace's alone.
+ *   ada_membrane_end_fwd      evaluates the TRUE residual b - A u from u itself, writes out and / or out64 (one of them is required), and per plane
+ *     residual (fp64, its max norm), iterations (int32, the steps taken before the freeze) and converged (uint8, residual <= tol).  Two launches.  x must
+ *     be begin's; the state is finished afterwards (begin starts the next solve).
+ *   workspace  workspace_bytes >= ada_membrane_workspace_bytes = 40 batch channels h w + 24 batch channels tiles + 48 batch channels + batch h w rounded
+ *     up to 8, tiles = ceil(h / TILE_H) ceil(w / TILE_W); 8-byte aligned (checked).  Every cell is written before it is read.
+ *   Limits: batch, channels, h, w >= 1; h, w <= 32767, batch, channels <= 65535 (else ADA_EUNSUPPORTED).  A null pointer, a bad tol or count, a workspace
+ *   that is too small: ADA_EINVAL before any launch.  Nothing is read back or allocated; the launch sequence depends on the arguments alone: legal inside
+ *   a stream capture.  Offsets into the maps are 64-bit.
+ * ---------------------------------------------------------------------------------------- */
+#define ADA_MEMBRANE_TILE_H 16         /* rows of a workgroup's tile: one partial sum per tile and plane */
+#define ADA_MEMBRANE_TILE_W 64         /* columns of a workgroup's tile */
+int ada_membrane_workspace_bytes(int32_t batch, int32_t channels, int32_t h, int32_t w, int64_t* bytes);
+int ada_membrane_begin_fwd(const float* x, const float* minus, const uint8_t* known, const uint8_t* domain, const float* guess, int32_t batch,
+                           int32_t channels, int32_t h, int32_t w, double tol, void* workspace, int64_t workspace_bytes, void* stream);
+int ada_membrane_iterate_fwd(int32_t batch, int32_t channels, int32_t h, int32_t w, int32_t iterations, uint8_t* frozen, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+int ada_membrane_end_fwd(const float* x, const float* plus, int32_t batch, int32_t channels, int32_t h, int32_t w, float* out, double* out64,
+                         double* residual, int32_t* iterations, uint8_t* converged, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Tiled inference for inputs larger than the network's native 518 x 518 (the reference squashes every
  * input to 518 x 518, infer.py:17,84).  ada_tile_blend_fwd merges the per-tile predictions:
  *   tiles     fp32 [B, T, tile_h, tile_w]; tile t covers rows origin_y[t].. and columns origin_x[t].. of the full map
